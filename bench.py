@@ -22,7 +22,11 @@ accumulated on device and reduced across GPUs with ONE all-gather (RCCL over xGM
 region.  Timing: barrier + synchronize on both sides, max over ranks.  Weak scaling: every GPU owns --batch
 worlds.
 
-Prints ONE JSON line (rank 0) with metric/value/roofline/cpu_baseline.  See DESIGN.md §Measurement.
+A plain run times exactly --steps steps of the headline measurement after --warmup untimed ones and prints ONE JSON line (rank 0) with
+metric / value / unit / higher_is_better / dtype / ms_per_step.  `--full` adds everything else the line used to carry: the per-kernel
+HIP events and the roofline, the secondary measurements (stage-0-only distribution, single stream, single call, four handles, host
+tensors), the CPU baseline, and repetition of the timed region until --min-seconds (0.25 s) have been timed.  See DESIGN.md §Measurement.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float64, world-major).
 """
 import argparse
 import json
@@ -37,8 +41,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # One process per GPU under torch.distributed.run: RCCL brings streams of its own.  They idle during the timed steps, but with the HIP runtime's
 # default of FOUR hardware queues per process an idle stream still owns a queue and two of the four slice streams then share one: measured
 # 4.27 against 6.66 M worlds*steps/s per GPU ("Throughput").  Eight queues give every stream its own again.  Read by the HIP
-# runtime when it initialises, i.e. before the first torch.cuda call below; a caller's own setting wins.
-if "WORLD_SIZE" in os.environ and not os.environ.get("GPU_MAX_HW_QUEUES"):
+# runtime when it initialises, i.e. before the first torch.cuda call below; a caller's own setting wins when it asks for at least as many
+# (an environment that pins the runtime's default of four would otherwise put the launcher path back to 4.27 M/s).
+if "WORLD_SIZE" in os.environ and int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 8:
     os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 import numpy as np  # noqa: E402
@@ -60,6 +65,27 @@ def csrc_sha16():
         h.update(f.encode()); h.update(open(os.path.join(d, f), "rb").read())
     h.update(open(os.path.join(ROOT, "include", "nimble_amd.h"), "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, per_world, shared):
+    """--dump-outputs: `per_world` name -> array whose LAST axis is the world (the library's [..][B] layout), written world-major
+    ([B, ..]) as out_dir/<name>.npy in float64; `shared` name -> array without a world axis, written as it is.  Above 64 MB in all, the
+    same fixed, seeded sample of worlds is taken from every per-world array and its indices are written as world_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.moveaxis(np.asarray(v, dtype=np.float64), -1, 0) for k, v in per_world.items()}
+    B = next(iter(arrays.values())).shape[0]
+    bytes_per_world = sum(a[0].nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - sum(np.asarray(v, dtype=np.float64).nbytes for v in shared.values())
+    if bytes_per_world * B > budget:
+        idx = np.sort(np.random.default_rng(0).choice(B, max(1, budget // (bytes_per_world + 8)), replace=False))   # (+8: its index)
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["world_index"] = idx.astype(np.float64)
+    arrays.update({k: np.asarray(v, dtype=np.float64) for k, v in shared.items()})
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def make_workload(name, B, seed, joint_noise):
@@ -174,6 +200,9 @@ def main():
     ap.add_argument("--workload", default="atlas20_contact")
     ap.add_argument("--joint-noise", type=float, default=0.02, help="pose noise of the metric distribution (SURVEY.md 8d: N(0, 0.02^2))")
     ap.add_argument("--easy-noise", type=float, default=0.002, help="pose noise of the secondary stage-0-only measurement (0 = skip it)")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel timing + roofline, the secondary measurements, the CPU baseline, "
+                    "and repetition of the timed region until --min-seconds (a plain run times exactly --steps steps once)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--streams", type=int, default=0, help="slices of the per-GPU batch, each a World on its own HIP stream (0 = auto: 4 from 4096 worlds, 2 from 2048)")
     ap.add_argument("--checkpoint-every", type=int, default=0, help="with --rollout: keep the backward records of K steps instead of T (the backward pass recomputes the other segments)")
@@ -182,11 +211,14 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true", help="diagnostic: timed region without the per-kernel HIP events")
     ap.add_argument("--spawn", action="store_true", help="go through the self-launch path (torch.distributed.run, one process per GPU, RCCL) even for --gpus 1")
     ap.add_argument("--no-single-stream", action="store_true", help="skip the secondary one-launch-per-kernel measurement")
-    ap.add_argument("--min-seconds", type=float, default=0.25, help="repeat the K-step timed region until this much time has been timed; the median repetition is reported")
+    ap.add_argument("--min-seconds", type=float, default=None, help="repeat the K-step timed region until this much time has been timed; the median "
+                    "repetition is reported (default: 0.25 with --full, else 0 = exactly one K-step region)")
     ap.add_argument("--max-reps", type=int, default=25)
     ap.add_argument("--max-contacts", type=int, default=0, help="diagnostic: contact slots per world of the model (0 = the workload's own, 8); 16 runs the "
                     "same worlds on the 48-row instantiation of the contact stage, 17..64 on the general one")
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 0.25 if args.full else 0.0
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -295,14 +327,16 @@ def main():
                         with torch.cuda.stream(stream):
                             ga_sum[:, lo:hi] += d["ga"][:, lo:hi]                                                   # the control vector is shared by all steps
                 world.join()
-                return shared_parameter_grad(ga_sum), d["status"]                                                 # ONE all-gather per timed region
+                outs = {"next_state": d["nxt"], "grad_state": d["gs"], "grad_action": d["ga"], "status": d["status"]}
+                return shared_parameter_grad(ga_sum), d["status"], outs                                           # ONE all-gather per timed region
             ga_total = [torch.zeros((k, hi - lo), dtype=torch.float64, device=dev) for (lo, hi) in bounds]
             status = [None] * len(bounds)
             if args.rollout > 0 and args.graph:      # the same pass replayed from ONE captured HIP graph (nimblephysics_amd.graph.GraphedRollout)
                 for _ in range(T):
                     graphed.replay()
                     ga_total[0] += graphed.grad_actions.sum(0)
-                return shared_parameter_grad(ga_total[0]), graphed.status[0]
+                outs = {"states": graphed.states, "grad_state0": graphed.grad_state0, "grad_actions": graphed.grad_actions, "status": graphed.status}
+                return shared_parameter_grad(ga_total[0]), graphed.status[0], outs
             if args.rollout > 0:      # cfg5-style: T-step trajectory, loss = |q_T|^2 + |v_T|^2, one shared control vector
                 for _ in range(T):
                     states, sv, st_all = world.rollout_soa(state0[0], action[0], T=args.rollout, want_saved=True, warm_start=True, checkpoint_every=args.checkpoint_every)
@@ -311,10 +345,12 @@ def main():
                     g0, ga = world.rollout_backward_soa(sv, gst)
                     ga_total[0] += ga.sum(0)
                     status[0] = st_all[0]        # the cold-start step (later steps are warm-started and resolve at stage 0)
-                return shared_parameter_grad(ga_total[0]), status[0]
+                outs = {"states": states, "grad_state0": g0, "grad_actions": ga, "status": st_all}
+                return shared_parameter_grad(ga_total[0]), status[0], outs
             main = streams[0]
             for st in streams[1:]:
                 st.wait_stream(main)
+            last = [None] * len(bounds)
             for _ in range(T):
                 for i, (w, st) in enumerate(zip(worlds, streams)):
                     with torch.cuda.stream(st):
@@ -322,9 +358,12 @@ def main():
                         nxt, sv, status[i] = w.step_soa(state0[i], action[i], want_saved=True)
                         gs, ga = w.backward_soa(sv, 2.0 * nxt)                     # d/ds' of |s'|^2
                         ga_total[i] += ga                                          # the control vector is shared by all steps
+                        last[i] = (nxt, gs, ga)
             for st in streams[1:]:
                 main.wait_stream(st)
-            return shared_parameter_grad(torch.cat(ga_total, 1)), torch.cat(status)   # ONE all-gather per timed region
+            outs = {nm: torch.cat([x[j] for x in last], 1) for j, nm in enumerate(("next_state", "grad_state", "grad_action"))}
+            outs["status"] = torch.cat(status)
+            return shared_parameter_grad(torch.cat(ga_total, 1)), torch.cat(status), outs   # ONE all-gather per timed region
 
         if warmup > 0:
             run(warmup)
@@ -338,7 +377,7 @@ def main():
         reps, rank_min = [], []
         while True:
             t0 = time.perf_counter()
-            grad, status = run(steps)
+            grad, status, outs = run(steps)
             sync()
             el = time.perf_counter() - t0
             if use_dist:
@@ -356,6 +395,11 @@ def main():
         tm = world.get_timing()
         world.set_timing(False)
         st = status.cpu().numpy().astype(np.uint32)
+        # what the caller of the timed path received in its last step (host copies, only when asked for: --dump-outputs)
+        dumped = None
+        if args.dump_outputs:
+            dumped = ({nm: t.double().cpu().numpy() for nm, t in outs.items()}, {"shared_action_grad": grad.double().cpu().numpy()})
+        del outs
         # (the handles - and the HIP streams they own - die with this frame: a later measurement starts with fresh streams.  The runtime maps
         #  streams to its four hardware queues in creation order; with the streams of an earlier handle still alive the two slices of a
         #  joined call shared a queue: `single_call` 3.85 instead of 5.9 M/s)
@@ -363,22 +407,26 @@ def main():
         dims = {"n": world.n, "m": world.m, "saved_bytes_per_world": int(world._L.nbl_saved_bytes(world._h, B) // B)}
         del deferred, graphed, worlds, world
         return {"elapsed": elapsed, "reps": reps, "rank_min": rank_min, "status": st, "timing": tm, "timing_period": timing_period, "md": md, "s": s_np, "a": a_np,
-                "desc": wl_desc, "dims": dims, "slices": n_slices}
+                "desc": wl_desc, "dims": dims, "slices": n_slices, "outputs": dumped}
 
     has_contact = args.workload.endswith("_contact")
     # The timed region is ONE model handle in deferred-join mode (round 6): `--streams k` (k > 0) goes back to round 5's
     # harness pattern - k Worlds, each on its own stream - which stays as a secondary figure (`four_handles`).
     one = args.streams == 0 and args.rollout == 0
+    kernel_timing = args.full and not args.no_kernel_timing       # per-kernel HIP events feed the roofline: --full only
     if one:
-        R = measure(args.joint_noise, args.steps, args.warmup, not args.no_kernel_timing, args.min_seconds, [(0, B)], streams[:1], one_handle=True)
+        R = measure(args.joint_noise, args.steps, args.warmup, kernel_timing, args.min_seconds, [(0, B)], streams[:1], one_handle=True)
     else:
-        R = measure(args.joint_noise, args.steps, args.warmup, not args.no_kernel_timing, args.min_seconds)
+        R = measure(args.joint_noise, args.steps, args.warmup, kernel_timing, args.min_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *R["outputs"])
+    # everything below the headline measurement is --full only
     easy = None
-    if has_contact and args.easy_noise > 0 and args.easy_noise != args.joint_noise:
+    if args.full and has_contact and args.easy_noise > 0 and args.easy_noise != args.joint_noise:
         # the easy distribution: every world resolves at LCP stage 0 (round 1's headline), half the steps, no kernel events
         easy = measure(args.easy_noise, max(1, args.steps // 2), min(args.warmup, 4), False)
     single = single_call = one_handle_deferred = None
-    if has_contact and len(bounds) > 1 and not args.no_single_stream:
+    if args.full and has_contact and len(bounds) > 1 and not args.no_single_stream:
         # the same batch as ONE launch per kernel per step (no stream slices): what the chain costs without the overlap of the slices
         single = measure(args.joint_noise, max(1, args.steps // 2), min(args.warmup, 4), False, 0.0, [(0, B)], streams[:1], slices=1)
         # ... and as ONE call per step with the library's own slicing (what a caller gets who hands over the whole batch at once)
@@ -387,7 +435,7 @@ def main():
         if one:
             one_handle_deferred = measure(args.joint_noise, args.steps, min(args.warmup, 4), False, 0.0)
     host_tensors = None
-    if has_contact and not args.no_single_stream and world_size == 1 and args.rollout == 0:
+    if args.full and has_contact and not args.no_single_stream and world_size == 1 and args.rollout == 0:
         # the reference's OWN calling convention (python/nimblephysics/timestep.py:31-40): float64 CPU tensors [B, 2n] / [B, k] in, CPU tensors
         # out, through the drop-in surface timestep() + .backward() of ONE World - pinned staging, asynchronous copies on the step's stream,
         # the two layout transposes, everything.  PCIe-inclusive: a secondary figure, never `value`.
@@ -420,79 +468,81 @@ def main():
         total_units = units_per_step * args.steps
         value = total_units / elapsed
         m_rows = 24 if dims["m"] > 0 else 0
-        kern = {kname: v["ms_sum"] / v["count"] for kname, v in tm["kernels"].items()}
-        if not kern:   # no per-kernel events (--no-kernel-timing, or the rollout entry points, which own their streams): whole-step figures
-            kern = {"whole_step": elapsed / args.steps * 1e3 / max(1, args.rollout)}
-        # algorithmic HBM bytes per world-step fwd+bwd (fp64) = 104 n + 16 m.
-        # Per launch of the step (all kernels of one forward + one backward): that figure x B worlds.
-        dom = max(kern, key=kern.get)
-        alg_step_bytes = (104 * n + 16 * m_rows) * B
-        slices = R["slices"]   # the batch is processed as slices on overlapping HIP streams:
-        alg_launch_bytes = alg_step_bytes / slices  # one kernel launch covers B / slices worlds (timed on slice 0)
-        step_kernel_ms = sum(kern.values())
-        # the dominant kernel is credited with the whole step's algorithmic traffic share it is responsible for:
-        # state/cotangent I/O is spread over the kernels, so the conservative per-kernel figure is
-        # (algorithmic bytes of one step) / (duration of the dominant kernel) -- an upper bound on its fraction.
-        achieved = alg_launch_bytes / (kern[dom] * 1e-3) / 1e9
-        traffic = None
-        prof_key = f"{args.workload}@{args.joint_noise:g}"
-        built = csrc_sha16()
-        stale = []
-        tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tfile):
-            try:
-                tj = json.load(open(tfile))
-                if tj.get("_csrc_sha16", {}).get(prof_key) == built:
-                    per_kernel = tj.get(prof_key, {})
-                    traffic = next((v for kname, v in per_kernel.items() if kname.split("<")[0] == dom), None)   # template suffixes: k<false>
-                elif prof_key in tj:
-                    stale.append("pmc_traffic.json")
-            except Exception:
-                traffic = None
-        # fp64 roofline: flop COUNTED by the SQ instruction counters (tools/profile.sh pass `fp64`, aggregated by
-        # tools/aggregate_profile.py into profiles/fp64_flops.json): 2 x FMA + ADD + MUL + TRANS wave-instructions x active lanes.
-        # Only counters taken on the kernels that are built right now are used (tag = hash of csrc/).
-        fp64 = None
-        ffile = os.path.join(ROOT, "profiles", "fp64_flops.json")
-        if os.path.exists(ffile):
-            try:
-                fj = json.load(open(ffile)).get(prof_key)
-                if fj and fj.get("csrc_sha16") == built:
-                    fl = float(fj["flops_per_world_step"])
-                    per_gpu_rate = value / world_size
-                    fp64 = {"flops_per_world_step": fl, "counted_by": fj.get("counted_by"), "csrc_sha16": built,
-                            "achieved_TFs": fl * per_gpu_rate / 1e12,
-                            "peak_TFs": FP64_PEAK_TFLOPS, "frac": fl * per_gpu_rate / 1e12 / FP64_PEAK_TFLOPS,
-                            "mfma_f64_wave_instr_per_world_step": fj.get("mfma_f64_wave_instr_per_world_step"),
-                            "valu_lane_utilisation": fj.get("valu_lane_utilisation")}
-                    # the dominant kernel on its own: its counted flop per launch / its average launch duration (HIP events)
-                    kd = next((v for kname, v in fj.get("kernels", {}).items() if kname.split("<")[0] == dom), None)
-                    if kd:
-                        k_tfs = kd["flops_per_world"] * (B // slices) / (kern[dom] * 1e-3) / 1e12
-                        fp64["dominant_kernel"] = {"kernel": dom, "flops_per_launch": kd["flops_per_world"] * (B // slices), "avg_launch_ms": kern[dom],
-                                                   "achieved_TFs": k_tfs, "frac": k_tfs / FP64_PEAK_TFLOPS, "avg_active_lanes": kd.get("avg_active_lanes")}
-                elif fj:
-                    stale.append("fp64_flops.json")
-            except Exception:
-                fp64 = None
-        hbm = {"kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-               "algorithmic_bytes_per_launch": alg_launch_bytes, "worlds_per_launch": B // slices,
-               "algorithmic_bytes_per_step": alg_step_bytes, "avg_launch_ms": kern[dom],
-               "whole_step_achieved_GBs": alg_step_bytes * max(1, args.rollout) / (elapsed / args.steps) / 1e9,
-               "whole_step_frac": alg_step_bytes * max(1, args.rollout) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS}
-        common = {"stream_slices": slices, "kernels_avg_ms": kern, "step_kernel_ms": step_kernel_ms, "timed_every_nth_step": timing_period,
-                  "csrc_sha16": built, "stale_counter_files_ignored": stale}
-        if fp64 is not None:
-            # ~300 flop per algorithmic byte - the fp64 vector ALU is the roof that binds, so it is the primary fraction
-            # (whole step: counted flop per world-step x measured rate); the HBM figures north_star asks for ride along under `hbm`.
-            roof = {"bound": "fp64", "kernel": "whole step (all kernels of one forward + one backward)", "achieved": fp64["achieved_TFs"],
-                    "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": fp64["frac"], "traffic": traffic, "fp64": fp64, "hbm": hbm, **common,
-                    "note": "fp64-ALU / latency bound (SURVEY.md 8d); peak = fp64 vector peak 78.6 TF (v_fma_f64 measured at 62.5 TF, "
-                            "v_mfma_f64 at 49.0 TF on this chip: docs/profiles_history/r02c_fp64_rate.jsonl); flop counted by SQ_INSTS_VALU_*_F64"}
-        else:
-            roof = {"bound": "hbm", **hbm, "fp64": None, **common,
-                    "note": "no fp64 flop count for the kernels built right now (profiles/fp64_flops.json is absent or was counted on other "
-                            "sources: run tools/profile.sh + tools/aggregate_profile.py): HBM fraction only; the path is fp64-ALU / latency bound"}
+        roof = None
+        if args.full:       # the per-kernel and roofline figures (their HIP events run with --full only)
+            kern = {kname: v["ms_sum"] / v["count"] for kname, v in tm["kernels"].items()}
+            if not kern:   # no per-kernel events (--no-kernel-timing, or the rollout entry points, which own their streams): whole-step figures
+                kern = {"whole_step": elapsed / args.steps * 1e3 / max(1, args.rollout)}
+            # algorithmic HBM bytes per world-step fwd+bwd (fp64) = 104 n + 16 m.
+            # Per launch of the step (all kernels of one forward + one backward): that figure x B worlds.
+            dom = max(kern, key=kern.get)
+            alg_step_bytes = (104 * n + 16 * m_rows) * B
+            slices = R["slices"]   # the batch is processed as slices on overlapping HIP streams:
+            alg_launch_bytes = alg_step_bytes / slices  # one kernel launch covers B / slices worlds (timed on slice 0)
+            step_kernel_ms = sum(kern.values())
+            # the dominant kernel is credited with the whole step's algorithmic traffic share it is responsible for:
+            # state/cotangent I/O is spread over the kernels, so the conservative per-kernel figure is
+            # (algorithmic bytes of one step) / (duration of the dominant kernel) -- an upper bound on its fraction.
+            achieved = alg_launch_bytes / (kern[dom] * 1e-3) / 1e9
+            traffic = None
+            prof_key = f"{args.workload}@{args.joint_noise:g}"
+            built = csrc_sha16()
+            stale = []
+            tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tfile):
+                try:
+                    tj = json.load(open(tfile))
+                    if tj.get("_csrc_sha16", {}).get(prof_key) == built:
+                        per_kernel = tj.get(prof_key, {})
+                        traffic = next((v for kname, v in per_kernel.items() if kname.split("<")[0] == dom), None)   # template suffixes: k<false>
+                    elif prof_key in tj:
+                        stale.append("pmc_traffic.json")
+                except Exception:
+                    traffic = None
+            # fp64 roofline: flop COUNTED by the SQ instruction counters (tools/profile.sh pass `fp64`, aggregated by
+            # tools/aggregate_profile.py into profiles/fp64_flops.json): 2 x FMA + ADD + MUL + TRANS wave-instructions x active lanes.
+            # Only counters taken on the kernels that are built right now are used (tag = hash of csrc/).
+            fp64 = None
+            ffile = os.path.join(ROOT, "profiles", "fp64_flops.json")
+            if os.path.exists(ffile):
+                try:
+                    fj = json.load(open(ffile)).get(prof_key)
+                    if fj and fj.get("csrc_sha16") == built:
+                        fl = float(fj["flops_per_world_step"])
+                        per_gpu_rate = value / world_size
+                        fp64 = {"flops_per_world_step": fl, "counted_by": fj.get("counted_by"), "csrc_sha16": built,
+                                "achieved_TFs": fl * per_gpu_rate / 1e12,
+                                "peak_TFs": FP64_PEAK_TFLOPS, "frac": fl * per_gpu_rate / 1e12 / FP64_PEAK_TFLOPS,
+                                "mfma_f64_wave_instr_per_world_step": fj.get("mfma_f64_wave_instr_per_world_step"),
+                                "valu_lane_utilisation": fj.get("valu_lane_utilisation")}
+                        # the dominant kernel on its own: its counted flop per launch / its average launch duration (HIP events)
+                        kd = next((v for kname, v in fj.get("kernels", {}).items() if kname.split("<")[0] == dom), None)
+                        if kd:
+                            k_tfs = kd["flops_per_world"] * (B // slices) / (kern[dom] * 1e-3) / 1e12
+                            fp64["dominant_kernel"] = {"kernel": dom, "flops_per_launch": kd["flops_per_world"] * (B // slices), "avg_launch_ms": kern[dom],
+                                                       "achieved_TFs": k_tfs, "frac": k_tfs / FP64_PEAK_TFLOPS, "avg_active_lanes": kd.get("avg_active_lanes")}
+                    elif fj:
+                        stale.append("fp64_flops.json")
+                except Exception:
+                    fp64 = None
+            hbm = {"kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                   "algorithmic_bytes_per_launch": alg_launch_bytes, "worlds_per_launch": B // slices,
+                   "algorithmic_bytes_per_step": alg_step_bytes, "avg_launch_ms": kern[dom],
+                   "whole_step_achieved_GBs": alg_step_bytes * max(1, args.rollout) / (elapsed / args.steps) / 1e9,
+                   "whole_step_frac": alg_step_bytes * max(1, args.rollout) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS}
+            common = {"stream_slices": slices, "kernels_avg_ms": kern, "step_kernel_ms": step_kernel_ms, "timed_every_nth_step": timing_period,
+                      "csrc_sha16": built, "stale_counter_files_ignored": stale}
+            if fp64 is not None:
+                # ~300 flop per algorithmic byte - the fp64 vector ALU is the roof that binds, so it is the primary fraction
+                # (whole step: counted flop per world-step x measured rate); the HBM figures north_star asks for ride along under `hbm`.
+                roof = {"bound": "fp64", "kernel": "whole step (all kernels of one forward + one backward)", "achieved": fp64["achieved_TFs"],
+                        "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": fp64["frac"], "traffic": traffic, "fp64": fp64, "hbm": hbm, **common,
+                        "note": "fp64-ALU / latency bound (SURVEY.md 8d); peak = fp64 vector peak 78.6 TF (v_fma_f64 measured at 62.5 TF, "
+                                "v_mfma_f64 at 49.0 TF on this chip: docs/profiles_history/r02c_fp64_rate.jsonl); flop counted by SQ_INSTS_VALU_*_F64"}
+            else:
+                roof = {"bound": "hbm", **hbm, "fp64": None, **common,
+                        "note": "no fp64 flop count for the kernels built right now (profiles/fp64_flops.json is absent or was counted on other "
+                                "sources: run tools/profile.sh + tools/aggregate_profile.py): HBM fraction only; the path is fp64-ALU / latency bound"}
         out = {
             "metric": "worlds*timesteps/sec fwd+bwd", "value": value, "unit": "worlds*timesteps/s",
             "n_gpus": world_size, "steps": args.steps, "warmup": args.warmup,
@@ -516,8 +566,9 @@ def main():
                        "lanes_resolved_at_lcp_stage0": float((st & 0x2).astype(bool).mean()) if m_rows else None,
                        "lanes_unresolved": float((st & 0x20).astype(bool).mean()),
                        "collective": "1 all-gather of the shared-control gradient per timed region"},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if easy is not None:
             est = easy["status"]
             esteps = max(1, args.steps // 2)
@@ -553,7 +604,7 @@ def main():
                         "out (the reference's own convention); the World's pinned staging buffers + asynchronous copies on the step's stream; torch CPU "
                         "intra-op threads = 1 for this leg (the default overruns the container's CFS quota, see bench.py).  Never `value`.",
                 "torch_cpu_threads": 1}
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(md, s_np, a_np)
             except Exception as e:  # the checker must never take the bench down

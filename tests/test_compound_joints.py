@@ -149,12 +149,11 @@ def test_property_tests_on_the_expanded_model():
     assert rel_err(r["grad_state"][0], fd) < 1e-6
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/data/skel/test"), reason="reference data not present")
 @pytest.mark.parametrize("name,ndof", [("test/single_pendulum_euler_joint.skel", 3), ("test/double_pendulum_euler_joint.skel", 6),
                                         ("test/serial_chain_eulerxyz_joint.skel", None), ("test/planar_joint.skel", None),
                                         ("test/translational_joints.skel", None)])
 def test_the_references_own_compound_joint_skel_files_load(name, ndof):
-    md = na.load_skel(os.path.join("/root/reference/data/skel", name))
+    md = na.load_skel(os.path.join(HERE, "golden", "reference_data", "data", "skel", name))     # the reference's own files, stored with the tests
     assert md.num_dofs == len([b for b in md.bodies if b.joint_type in ("revolute", "prismatic")]) + 6 * sum(b.joint_type == "free" for b in md.bodies)
     if ndof is not None:
         assert md.num_dofs == ndof

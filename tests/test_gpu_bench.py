@@ -21,7 +21,7 @@ def _run(args):
 
 
 def test_bench_self_launch_path_one_gpu():
-    d = _run(["--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1", "--batch", "512", "--no-cpu-baseline"])
+    d = _run(["--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1", "--batch", "512", "--no-cpu-baseline", "--full"])
     assert d["n_gpus"] == 1 and d["config"]["rccl_world_size"] == 1           # RCCL process group of one rank was initialised
     assert d["value"] > 0 and d["steps"] == 2 and d["scaling"] == "weak"
     assert d["config"]["joint_noise"] == 0.02 and 0.3 < d["config"]["lanes_resolved_at_lcp_stage0"] < 0.7
@@ -40,6 +40,24 @@ def test_bench_cfg5_workload_is_selectable():
     d = _run(["--workload", "atlas33_contact", "--rollout", "8", "--steps", "1", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--easy-noise", "0"])
     assert d["config"]["n_dofs"] == 33 and d["config"]["rollout_T"] == 8 and d["value"] > 0
     assert "N(0,0.02^2)" in d["config"]["workload"]
+
+
+def test_plain_bench_times_exactly_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full): ONE timed region of exactly --steps steps, the headline fields and nothing of what --full measures; with
+    --dump-outputs the last step's next state, gradients and status of every world as float64 .npy files."""
+    d = _run(["--steps", "3", "--warmup", "1", "--batch", "512", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and d["reps"] == 1 and len(d["reps_ms_per_step"]) == 1 and d["ms_per_step"] > 0
+    assert d["metric"] == "worlds*timesteps/sec fwd+bwd" and d["unit"] == "worlds*timesteps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert not {"secondary", "roofline", "cpu_baseline"} & set(d)
+    import numpy as np
+    n2 = 2 * d["config"]["n_dofs"]
+    arrays = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(arrays) == {"next_state", "grad_state", "grad_action", "status", "shared_action_grad"}
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["next_state"].shape == arrays["grad_state"].shape == (512, n2) and arrays["status"].shape == (512,)
+    assert arrays["grad_action"].shape[0] == 512 and arrays["shared_action_grad"].shape == arrays["grad_action"].shape[1:]
+    assert np.allclose(arrays["shared_action_grad"], 3 * arrays["grad_action"].sum(0), rtol=1e-9, atol=1e-12)   # 3 identical cold steps
 
 
 def test_scale_curve_tool_at_one_gpu():

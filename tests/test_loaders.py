@@ -101,14 +101,15 @@ def test_urdf_floating_and_planar_joints_like_dart_loader(tmp_path):
     assert md.num_dofs == 6 + 3 + 1 + 6
 
 
-REF_URDF = "/root/reference/data/sdf/atlas/atlas_v3_box_colliders.urdf"
+# the reference's own data files, stored with the tests (tests/golden/reference_data/README.md)
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
+REF_URDF = os.path.join(REF_DATA, "data/sdf/atlas/atlas_v3_box_colliders.urdf")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_URDF), reason="reference tree not present (GPU box)")
 def test_committed_atlas_descriptions_are_reproducible_from_the_reference_urdf():
     arms = [f"{s}_arm_{j}" for s in "lr" for j in ("shy", "shx", "ely", "elx", "wry", "wrx")]
     md = na.load_urdf(REF_URDF, "atlas20", weld_joints=set(arms + ["back_bkz"]))
-    ground = na.load_urdf("/root/reference/data/sdf/atlas/ground.urdf", "ground")
+    ground = na.load_urdf(os.path.join(REF_DATA, "data/sdf/atlas/ground.urdf"), "ground")
     both = na.with_ground(md, ground)
     here = os.path.join(os.path.dirname(na.__file__), "data", "atlas20_ground.json")
     assert json.loads(json.dumps(both.to_json())) == json.load(open(here))
@@ -211,13 +212,11 @@ def test_skel_model_steps_like_the_hand_built_one(tmp_path):
     assert np.all(np.isfinite(nxt)) and not np.allclose(nxt, s)
 
 
-REF_SKEL = "/root/reference/data/skel/test"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_SKEL), reason="reference tree not present (GPU box)")
-def test_committed_cfg1_cfg4_descriptions_are_reproducible_from_the_reference_skel_files():
+def test_committed_cfg1_cfg4_descriptions_are_reproducible_from_the_reference_skel_files(monkeypatch):
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import urdf_to_model
+    monkeypatch.setattr(urdf_to_model, "REF", REF_DATA)
     from urdf_to_model import skel_models
     pend, stack = skel_models()
     data = os.path.join(os.path.dirname(na.__file__), "data")

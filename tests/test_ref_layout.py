@@ -2,6 +2,8 @@
 skeleton keeps that skeleton's coordinates in `World::getState()` (dart/simulation/World.cpp:2016-2047); the loader welds the skeleton at its
 zero configuration and records the reference's coordinate order (ModelDescription.ref_dof_mobile), and the drop-in surface speaks the
 reference's layout through nimblephysics_amd/ref_layout.py.  CPU half: the loader's bookkeeping and the layout arithmetic."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -75,11 +77,10 @@ def test_layout_arithmetic():
     assert lay.device_action_map([0, 1, 2, 4]) == [0, 1, 2] and lay.action_columns([0, 1, 2, 4]) == [1, 2, 3]
 
 
-REF_SKEL = "/root/reference/data/skel"
+REF_SKEL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data", "data", "skel")   # the reference's own files
 JOINT_DOFS = {"free": 6, "ball": 3, "euler": 3, "revolute": 1, "prismatic": 1, "screw": 1, "universal": 2, "translational": 3, "translational2d": 2, "planar": 3, "weld": 0}
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REF_SKEL), reason="the reference's data files are not here")
 @pytest.mark.parametrize("name", ["cubes.skel", "fullbody1.skel", "cartpole.skel", "ground.skel", "two_cubes.skel", "test/box_stacking.skel", "test/file_info_world_test.skel"])
 def test_the_state_length_of_the_references_own_skel_files(name):
     """getStateSize() of the drop-in surface = 2 x the coordinates of EVERY skeleton of the file, immobile ones included - what

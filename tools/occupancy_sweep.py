@@ -2,7 +2,7 @@
 (here, hipcc cross-compiles) and, on the GPU box, runs the bench line of each.
 
   python tools/occupancy_sweep.py build            # -> build/variants/libnimble_amd_<tag>.so
-  python tools/occupancy_sweep.py run [out.json]   # on the GPU: bench.py --no-cpu-baseline per variant
+  python tools/occupancy_sweep.py run [out.json]   # on the GPU: bench.py --full --no-cpu-baseline per variant
 """
 import json
 import os
@@ -46,7 +46,7 @@ def run(out_path, extra):
         if not os.path.exists(lib):
             continue
         env = dict(os.environ, NBL_LIB_PATH=lib)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--easy-noise", "0", *extra], env=env, capture_output=True, text=True)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--easy-noise", "0", *extra], env=env, capture_output=True, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if not line:
             res[tag] = {"error": p.stderr[-400:]}

@@ -45,7 +45,8 @@ def main():
     assert visible >= 1, "no GPU visible"
     ns = [n for n in args.gpus if n <= visible]
     skipped = [n for n in args.gpus if n > visible]
-    common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch), "--no-cpu-baseline", "--no-single-stream", "--easy-noise", "0"]
+    common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch), "--min-seconds", "0.25", "--no-cpu-baseline",
+              "--no-single-stream", "--easy-noise", "0"]
 
     plain = run_bench(["--gpus", "1"] + common)
     rows = []
