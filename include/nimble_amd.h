@@ -206,7 +206,9 @@ const char* nbl_last_error(void);
  *   minor 4: max_contacts up to 64 (64 colliders, 512 pairs: the general instantiation); the Dantzig self-test takes n <= 192;
  *            nbl_workspace_bytes of such a model includes 1.5 MB of scratch matrices per world; max_contacts 65 .. 128: a second general
  *            instantiation of 384 rows (5.9 MB of scratch per world), the Dantzig self-test then takes n <= 384.
- *   minor 5: + nbl_set_deferred_join, nbl_slice_stream, nbl_fork_slices, nbl_join_slices (one handle, slices that are not joined per call). */
+ *   minor 5: + nbl_set_deferred_join, nbl_slice_stream, nbl_fork_slices, nbl_join_slices (one handle, slices that are not joined per call);
+ *            + nbl_kin_map_create, nbl_kin_map_destroy, nbl_kin_map_dim, nbl_kinematics_forward, nbl_kinematics_backward (world-space
+ *            kinematics of body frames, below: added without a new minor number - a caller that needs them looks the symbols up). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -422,6 +424,44 @@ int32_t nbl_set_deferred_join(nbl_model* m, int32_t enabled);
 int32_t nbl_slice_stream(nbl_model* m, int64_t B, int32_t slice, void** stream, int64_t* first_world, int64_t* end_world);
 int32_t nbl_fork_slices(nbl_model* m, void* stream);
 int32_t nbl_join_slices(nbl_model* m, void* stream);
+/*
+ * World-space kinematics of body frames: the reference's IKMapping (dart/neural/IKMapping.{hpp,cpp}) and the vector-Jacobian products
+ * of nimble.map_to_pos / nimble.map_to_vel (python/nimblephysics/mapping.py:8-101), for B worlds at once.
+ *
+ * A map is a list of ENTRIES made against a model; several maps may coexist on one handle.  An entry is a frame F fixed in one body of
+ * the description the model was created from (`body`: its index there - the description has no welds: a welded body is its merged
+ * body plus a constant offset; -1 = the world: a constant entry), F = W_body T_offset.  The library resolves its internal bodies (the
+ * entry sits on the body that carries T_cj: the z body of a ball triple, the last body of a free chain).  Its rows, concatenated in
+ * the order of the entries (IKMapping::getPositionsInPlace / getVelocitiesInPlace, IKMapping.cpp:146-232):
+ *   NBL_KIN_SPATIAL  6 rows  position: logMap(R_F), then p_F     velocity: [w; v] = getSpatialVelocity(World, World) (Frame.cpp:163-178)
+ *   NBL_KIN_LINEAR   3 rows  position: p_F                        velocity: v, the velocity of F's origin in world coordinates
+ *   NBL_KIN_ANGULAR  3 rows  position: logMap(R_F)                velocity: w, the angular velocity in world coordinates
+ * (IKMapping's COM entries have no public constructor in the reference and are not offered.)  At most 64 entries (P <= 384 rows):
+ * more is NBL_E_BADARG.  T_offset: [count][12], R row-major then p; NULL = identity for every entry.  Registration uploads the entries
+ * once (synchronous); destroy a map before the model it was made for.
+ */
+#define NBL_KIN_SPATIAL 0 /* 6 rows: logMap(R) then p */
+#define NBL_KIN_LINEAR 1  /* 3 rows: p */
+#define NBL_KIN_ANGULAR 2 /* 3 rows: logMap(R) */
+typedef struct nbl_kin_map nbl_kin_map; /* opaque */
+int32_t nbl_kin_map_create(nbl_model* m, int32_t count, const int32_t* kind, const int32_t* body, const double* T_offset,
+                           nbl_kin_map** out);
+void nbl_kin_map_destroy(nbl_kin_map* k);
+int32_t nbl_kin_map_dim(const nbl_kin_map* k); /* P: the rows of the mapped vector (IKMapping::getPosDim = getVelDim) */
+/* The mapped positions pos [P][B] and / or velocities vel [P][B] (either may be NULL) of the states state [2n][B] (DEVICE pointers, the
+ * layout of nbl_step_forward; B may be (T + 1) x worlds: a whole rollout in one call).  Replaces IKMapping::getPositions /
+ * getVelocities after World::setState.  Stream-ordered on `stream`, no device synchronisation, no workspace; it does not use the
+ * handle's slices (deferred join does not apply).  Bit-reproducible, independent of B and of a world's place in the batch. */
+int32_t nbl_kinematics_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, double* pos, double* vel, void* stream);
+/* The vector-Jacobian products: grad_state [2n][B] = (accumulate: +=) [Jpos^T grad_pos; Jvel^T grad_vel].  Jpos =
+ * IKMapping::getPosJacobian (IKMapping.cpp:371-416: Skeleton::getWorldPositionJacobian, Skeleton.cpp:11010-11060 - the joints' position
+ * screws, the angular rows through dLogMap: the exact derivative of the rows above), Jvel = getVelJacobian (:429-473, getWorldJacobian).
+ * A NULL grad_pos / grad_vel contributes nothing to its block.  As MapToPosLayer / MapToVelLayer (mapping.py:34-44, 81-92), the velocity
+ * block carries Jvel^T grad_vel only: the dependence of J v on the positions is left out.  The angular rows follow logMap's regular
+ * branch up to theta = pi - 1e-6 (dLogMap's special branch there, Geometry.cpp:764-, is not restated).  Stream-ordered like
+ * nbl_kinematics_forward; no atomics: bit-reproducible. */
+int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* grad_pos,
+                                const double* grad_vel, double* grad_state, int32_t accumulate, void* stream);
 /* enabled = 0: off (and reset); 1: HIP events around every kernel launch; N > 1: around the launches of every N-th forward /
  * backward call only (sampling keeps the perturbation of a timed region below 1 %). */
 int32_t nbl_set_timing(nbl_model* m, int32_t enabled);

@@ -112,6 +112,16 @@ def lib():
     L.nbl_selftest_pinv.restype = C.c_int32
     L.nbl_selftest_pinv_rows.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp]
     L.nbl_selftest_pinv_rows.restype = C.c_int32
+    L.nbl_kin_map_create.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(vp)]
+    L.nbl_kin_map_create.restype = C.c_int32
+    L.nbl_kin_map_destroy.argtypes = [vp]
+    L.nbl_kin_map_destroy.restype = None
+    L.nbl_kin_map_dim.argtypes = [vp]
+    L.nbl_kin_map_dim.restype = C.c_int32
+    L.nbl_kinematics_forward.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp]
+    L.nbl_kinematics_forward.restype = C.c_int32
+    L.nbl_kinematics_backward.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int32, vp]
+    L.nbl_kinematics_backward.restype = C.c_int32
     _lib = L
     return L
 
@@ -124,6 +134,7 @@ EXPORTED_SYMBOLS = [
     "nbl_rollout_checkpoint_bytes", "nbl_rollout_forward_checkpointed", "nbl_rollout_backward_checkpointed",
     "nbl_get_timing", "nbl_kernel_count", "nbl_kernel_name", "nbl_kernel_timing", "nbl_selftest_lcp_dantzig", "nbl_selftest_lcp_dantzig_timed", "nbl_selftest_lcp_cascade", "nbl_selftest_pinv",
     "nbl_model_max_contacts", "nbl_selftest_pinv_rows",
+    "nbl_kin_map_create", "nbl_kin_map_destroy", "nbl_kin_map_dim", "nbl_kinematics_forward", "nbl_kinematics_backward",
 ]
 
 

@@ -69,6 +69,12 @@
 #define nbl_version NBL_V(nbl_version)
 #define nbl_workspace_bytes NBL_V(nbl_workspace_bytes)
 #define nbl_model_max_contacts NBL_V(nbl_model_max_contacts)
+#define nbl_kin_map NBL_V(nbl_kin_map)
+#define nbl_kin_map_create NBL_V(nbl_kin_map_create)
+#define nbl_kin_map_destroy NBL_V(nbl_kin_map_destroy)
+#define nbl_kin_map_dim NBL_V(nbl_kin_map_dim)
+#define nbl_kinematics_forward NBL_V(nbl_kinematics_forward)
+#define nbl_kinematics_backward NBL_V(nbl_kinematics_backward)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

@@ -30,6 +30,7 @@
 
 #include "model_dev.hpp"
 #include "spatial_dev.hpp"
+#include "kinematics_dev.hpp"   // cT, jointTwist, jointRelTransform, applyHt
 
 namespace NBL_NS {
 
@@ -224,63 +225,6 @@ template <class C> DEV void stS6(const C& c, int body, int slot, const S6& A) {
 template <class C> DEV void addS6(const C& c, int body, int slot, const S6& A) {
 #pragma unroll
   for (int k = 0; k < 21; k++) accAdd(wsAt(c, body, slot + k), A.a[k], c);
-}
-
-DEV T12 cT(const double* t) {  // wave-uniform constant -> scalar loads
-  T12 T;
-#pragma unroll
-  for (int k = 0; k < 9; k++) T.R.m[k] = t[k];
-  T.p = mk3(t[9], t[10], t[11]);
-  return T;
-}
-DEV S6 cS6(const double* g) {
-  S6 A;
-#pragma unroll
-  for (int k = 0; k < 21; k++) A.a[k] = g[k];
-  return A;
-}
-DEV V6 cV6(const double* s) { return mk6(mk3(s[0], s[1], s[2]), mk3(s[3], s[4], s[5])); }
-
-// joint twist S*dq in the child frame
-DEV V6 jointTwist(const DevBody& bd, const double* __restrict__ v, int64_t B, int64_t b) {
-  if (bd.jtype == JT_FREE) {
-    V6 x = mk6(mk3(v[(bd.dofOff + 0) * B + b], v[(bd.dofOff + 1) * B + b], v[(bd.dofOff + 2) * B + b]),
-               mk3(v[(bd.dofOff + 3) * B + b], v[(bd.dofOff + 4) * B + b], v[(bd.dofOff + 5) * B + b]));
-    return AdT(cT(bd.Tcj), x);  // S = Ad(T_cj), FreeJoint.cpp:1049-1056
-  }
-  return v[bd.dofOff * B + b] * cV6(bd.S);
-}
-
-// T_parent->child of one body at the positions q ([n][B]): T_pj Q(q) T_cj^-1 with Q of the joint type (RevoluteJoint.cpp:203-211,
-// PrismaticJoint, ScrewJoint.cpp:217-232, FreeJoint.cpp:74-81, BallJoint.cpp:91-95; ball joints and free joints below the root are
-// chains of coincident single-axis bodies whose first one carries the exponential map).  The same expressions as the tree kernels'
-// first sweep; used by the narrow phase when it runs next to the forward tree kernel instead of after it.
-DEV T12 jointRelTransform(const DevBody& bd, const double* __restrict__ q, int64_t B, int64_t b) {
-  T12 Q;
-  if (bd.jtype == JT_REVOLUTE) {
-    const double qi = q[bd.dofOff * B + b];
-    Q.R = expAngular(mk3(bd.axis[0] * qi, bd.axis[1] * qi, bd.axis[2] * qi));
-    Q.p = mk3(0, 0, 0);
-  } else if (bd.jtype == JT_PRISMATIC) {
-    const double qi = q[bd.dofOff * B + b];
-    Q.R = eye3();
-    Q.p = mk3(bd.axis[0] * qi, bd.axis[1] * qi, bd.axis[2] * qi);
-  } else if (bd.jtype == JT_SCREW) {
-    const double qi = q[bd.dofOff * B + b], hq = bd.screwRate * qi;
-    Q.R = expAngular(mk3(bd.axis[0] * qi, bd.axis[1] * qi, bd.axis[2] * qi));
-    Q.p = mk3(bd.axis[0] * hq, bd.axis[1] * hq, bd.axis[2] * hq);
-  } else if (bd.jtype == JT_FREEC) {
-    const int o = bd.dofOff;
-    Q.R = bd.ballComp == 0 ? expMapRot(mk3(q[(o + 0) * B + b], q[(o + 1) * B + b], q[(o + 2) * B + b])) : eye3();
-    Q.p = bd.ballComp == 0 ? mk3(q[(o + 3) * B + b], q[(o + 4) * B + b], q[(o + 5) * B + b]) : mk3(0, 0, 0);
-  } else if (bd.jtype == JT_BALL) {
-    Q.R = bd.ballComp == 0 ? expMapRot(mk3(q[(bd.dofOff + 0) * B + b], q[(bd.dofOff + 1) * B + b], q[(bd.dofOff + 2) * B + b])) : eye3();
-    Q.p = mk3(0, 0, 0);
-  } else {
-    Q.R = expMapRot(mk3(q[(bd.dofOff + 0) * B + b], q[(bd.dofOff + 1) * B + b], q[(bd.dofOff + 2) * B + b]));
-    Q.p = mk3(q[(bd.dofOff + 3) * B + b], q[(bd.dofOff + 4) * B + b], q[(bd.dofOff + 5) * B + b]);
-  }
-  return mulT(mulT(cT(bd.Tpj), Q), cT(bd.TcjInv));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -574,31 +518,6 @@ DEV void minvSweeps(const C& c, RhsFn rhsAt) {
     }
     stV6(c, i, WS_W, W);
   });
-}
-
-// Position-space Jacobian transpose of joint i applied to a body-frame adjoint xi:  H_i^T xi
-// (H = S for 1-DOF joints; free joint: Ad(T_cj) blkdiag(expMapJac(r)^T, R^T), FreeJoint.cpp:790-823)
-DEV void applyHt(const DevBody& bd, const double* __restrict__ q, int64_t B, int64_t b, V6 xi, double* out) {
-  if (bd.jtype == JT_BALL) {
-    // ball joint (BallJoint.cpp:282-289): H = [expMapJac(q)^T; 0] in the frame of the x body of the triple; xi = THAT body's adjoint
-    const int d0 = bd.dofOff - bd.ballComp;
-    const V3 y = mul(expMapJac(mk3(q[(int64_t)(d0 + 0) * B + b], q[(int64_t)(d0 + 1) * B + b], q[(int64_t)(d0 + 2) * B + b])), xi.w);
-    out[0] = bd.ballComp == 0 ? y.x : (bd.ballComp == 1 ? y.y : y.z);
-    return;
-  }
-  if (bd.jtype == JT_FREEC) {
-    // free joint below the root (FreeJoint.cpp:790-823): H = blkdiag(expMapJac(r)^T, R^T) in the frame of the first of its six bodies
-    const int d0 = bd.dofOff - bd.ballComp, cmp = bd.ballComp;
-    const V3 r = mk3(q[(int64_t)(d0 + 0) * B + b], q[(int64_t)(d0 + 1) * B + b], q[(int64_t)(d0 + 2) * B + b]);
-    out[0] = cmp < 3 ? pick3(mul(expMapJac(r), xi.w), cmp) : pick3(mul(expMapRot(r), xi.v), cmp - 3);
-    return;
-  }
-  if (bd.jtype != JT_FREE) { out[0] = dot(cV6(bd.S), xi); return; }
-  const int o = bd.dofOff;
-  V6 y = dAdT(cT(bd.Tcj), xi);
-  V3 r = mk3(q[(o + 0) * B + b], q[(o + 1) * B + b], q[(o + 2) * B + b]);
-  V3 qbr = mul(expMapJac(r), y.w), qbp = mul(expMapRot(r), y.v);
-  out[0] = qbr.x; out[1] = qbr.y; out[2] = qbr.z; out[3] = qbp.x; out[4] = qbp.y; out[5] = qbp.z;
 }
 
 // Reverse-mode Newton-Euler sweep at (q, v, qdd) with joint adjoint lambda (WS_UIMP/WS_W from

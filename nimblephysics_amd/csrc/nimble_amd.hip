@@ -25,6 +25,7 @@
 #endif
 #include "coop_tree.hip"
 #include "inertia_backward.hip"
+#include "kinematics.hip"
 
 using namespace NBL_NS;
 
@@ -1585,6 +1586,110 @@ int32_t nbl_kernel_timing(nbl_model* m, int32_t i, double* ms_sum, int64_t* coun
   if (rc != NBL_OK) return rc;
   if (ms_sum) *ms_sum = m->kMs[i];
   if (count) *count = m->kCount[i];
+  return NBL_OK;
+}
+
+// ---- world-space kinematics of body frames (IKMapping, map_to_pos / map_to_vel; csrc/kinematics.hip) ----------------------------------
+struct nbl_kin_map {
+  int device = 0;
+  int count = 0, P = 0, n = 0, nb = 0;   // entries, mapped rows, DOFs and device bodies of the model it was made for
+  void* dBuf = nullptr;                  // [count] DevKinEntry, then the ancestor chains (int32 device bodies, root -> entry body)
+  DevKinEntry* dEntries = nullptr;
+  int32_t* dPath = nullptr;
+};
+
+int32_t nbl_kin_map_create(nbl_model* m, int32_t count, const int32_t* kind, const int32_t* body, const double* T_offset, nbl_kin_map** out) {
+  if (!m || !out || !kind || !body) return fail(NBL_E_BADARG, "null argument");
+  *out = nullptr;
+  if (count < 1) return fail(NBL_E_BADARG, "a kinematics map needs at least one entry");
+  if (count > KIN_MAX_ENTRIES)
+    return fail(NBL_E_BADARG, "a kinematics map holds at most " + std::to_string(KIN_MAX_ENTRIES) + " entries (" +
+                                  std::to_string(6 * KIN_MAX_ENTRIES) + " rows); got " + std::to_string(count));
+  std::vector<DevKinEntry> he(count);
+  std::vector<int32_t> path;
+  int row = 0;
+  for (int k = 0; k < count; k++) {
+    if (kind[k] != NBL_KIN_SPATIAL && kind[k] != NBL_KIN_LINEAR && kind[k] != NBL_KIN_ANGULAR)
+      return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": kind must be NBL_KIN_SPATIAL, NBL_KIN_LINEAR or NBL_KIN_ANGULAR");
+    if (body[k] < -1 || body[k] >= m->userBodies)
+      return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": body " + std::to_string(body[k]) + " out of range [-1, " + std::to_string(m->userBodies) + ")");
+    DevKinEntry& e = he[k];
+    std::memset(&e, 0, sizeof(e));
+    e.kind = kind[k];
+    e.row = row;
+    row += kinRows(kind[k]);
+    static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    for (int c = 0; c < 12; c++) e.T[c] = T_offset ? T_offset[12 * k + c] : I12[c];
+    for (int c = 0; c < 12; c++)
+      if (!std::isfinite(e.T[c])) return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": non-finite offset transform");
+    // the ancestor chain of the device body that carries T_cj (the z body of a ball triple, the last body of a free chain), root first
+    std::vector<int32_t> chain;
+    for (int i = body[k] < 0 ? -1 : m->deviceBody(body[k]); i >= 0; i = m->hBodies[i].parent) chain.push_back(i);
+    e.pathBegin = (int32_t)path.size();
+    e.pathLen = (int32_t)chain.size();
+    path.insert(path.end(), chain.rbegin(), chain.rend());
+  }
+  nbl_kin_map* km = new nbl_kin_map();
+  km->device = m->device; km->count = count; km->P = row; km->n = m->n; km->nb = m->nb;
+  const size_t eb = sizeof(DevKinEntry) * count, bytes = eb + sizeof(int32_t) * std::max<size_t>(path.size(), 1);
+  std::vector<char> img(bytes, 0);
+  std::memcpy(img.data(), he.data(), eb);
+  if (!path.empty()) std::memcpy(img.data() + eb, path.data(), sizeof(int32_t) * path.size());
+  {
+    DeviceGuard guard(m->device);
+    hipError_t e = guard.ok ? hipMalloc(&km->dBuf, bytes) : hipErrorInvalidDevice;
+    if (e == hipSuccess) e = hipMemcpy(km->dBuf, img.data(), bytes, hipMemcpyHostToDevice);   // (registration time: synchronous)
+    if (e != hipSuccess) {
+      const std::string msg = std::string("kinematics map upload: ") + hipGetErrorString(e);
+      if (km->dBuf) (void)hipFree(km->dBuf);
+      delete km;
+      return fail(NBL_E_HIP, msg);
+    }
+  }
+  km->dEntries = (DevKinEntry*)km->dBuf;
+  km->dPath = (int32_t*)((char*)km->dBuf + eb);
+  *out = km;
+  return NBL_OK;
+}
+
+void nbl_kin_map_destroy(nbl_kin_map* k) {
+  if (!k) return;
+  if (k->dBuf) {
+    DeviceGuard guard(k->device);
+    (void)hipFree(k->dBuf);   // (waits for launches that still read it)
+  }
+  delete k;
+}
+
+int32_t nbl_kin_map_dim(const nbl_kin_map* k) { return k ? k->P : 0; }
+
+static int32_t kinCheck(const nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state) {
+  if (!m || !k || !state) return fail(NBL_E_BADARG, "null argument");
+  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  if (B <= 0) return fail(NBL_E_BADARG, "B must be positive");
+  if ((B + KIN_BLOCK - 1) / KIN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  return NBL_OK;
+}
+
+int32_t nbl_kinematics_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, double* pos, double* vel, void* stream) {
+  const int32_t rc = kinCheck(m, k, B, state);
+  if (rc != NBL_OK) return rc;
+  if (!pos && !vel) return NBL_OK;
+  hipLaunchKernelGGL(k_kinematics_fwd, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, pos, vel);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* grad_pos,
+                                const double* grad_vel, double* grad_state, int32_t accumulate, void* stream) {
+  const int32_t rc = kinCheck(m, k, B, state);
+  if (rc != NBL_OK) return rc;
+  if (!grad_state) return fail(NBL_E_BADARG, "null argument");
+  hipLaunchKernelGGL(k_kinematics_vjp, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, grad_pos,
+                     grad_vel, grad_state, accumulate ? 1 : 0);
+  HIP_TRY(hipGetLastError());
   return NBL_OK;
 }
 

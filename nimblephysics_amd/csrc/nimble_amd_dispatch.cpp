@@ -63,7 +63,12 @@
   int32_t nbl_get_timing##S(void*, double*, int64_t*, double*, int64_t*);                                                                  \
   int32_t nbl_kernel_count##S(void);                                                                                                       \
   const char* nbl_kernel_name##S(int32_t);                                                                                                 \
-  int32_t nbl_kernel_timing##S(void*, int32_t, double*, int64_t*);
+  int32_t nbl_kernel_timing##S(void*, int32_t, double*, int64_t*);                                                                         \
+  int32_t nbl_kin_map_create##S(void*, int32_t, const int32_t*, const int32_t*, const double*, void**);                                    \
+  void nbl_kin_map_destroy##S(void*);                                                                                                      \
+  int32_t nbl_kin_map_dim##S(const void*);                                                                                                 \
+  int32_t nbl_kinematics_forward##S(void*, const void*, int64_t, const double*, double*, double*, void*);                                  \
+  int32_t nbl_kinematics_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, double*, int32_t, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -114,6 +119,11 @@ struct Variant {
   int32_t (*set_timing)(void*, int32_t);
   int32_t (*get_timing)(void*, double*, int64_t*, double*, int64_t*);
   int32_t (*kernel_timing)(void*, int32_t, double*, int64_t*);
+  int32_t (*kin_map_create)(void*, int32_t, const int32_t*, const int32_t*, const double*, void**);
+  void (*kin_map_destroy)(void*);
+  int32_t (*kin_map_dim)(const void*);
+  int32_t (*kinematics_forward)(void*, const void*, int64_t, const double*, double*, double*, void*);
+  int32_t (*kinematics_backward)(void*, const void*, int64_t, const double*, const double*, const double*, double*, int32_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -123,13 +133,18 @@ struct Variant {
    nbl_rollout_checkpoint_bytes##S, nbl_rollout_forward_checkpointed##S, nbl_rollout_backward_checkpointed##S,                               \
    nbl_selftest_lcp_dantzig_timed##S, nbl_selftest_pinv_rows##S, nbl_set_launch_lanes##S, nbl_set_slices##S, nbl_slices_for##S,               \
    nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
-   nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S}
+   nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_kin_map_create##S, nbl_kin_map_destroy##S, nbl_kin_map_dim##S,          \
+   nbl_kinematics_forward##S, nbl_kinematics_backward##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
 
 struct nbl_model {
   const Variant* v;   // the instantiation that owns `impl`
+  void* impl;
+};
+struct nbl_kin_map {
+  const Variant* v;   // the instantiation of the model it was made against
   void* impl;
 };
 
@@ -308,5 +323,32 @@ int32_t nbl_get_timing(nbl_model* m, double* fwd_ms_sum, int64_t* fwd_count, dou
 int32_t nbl_kernel_count(void) { return nbl_kernel_count_c8(); }
 const char* nbl_kernel_name(int32_t i) { return nbl_kernel_name_c8(i); }
 int32_t nbl_kernel_timing(nbl_model* m, int32_t i, double* ms_sum, int64_t* count) { return NBL_FWD(m, kernel_timing, i, ms_sum, count); }
+
+int32_t nbl_kin_map_create(nbl_model* m, int32_t count, const int32_t* kind, const int32_t* body, const double* T_offset, nbl_kin_map** out) {
+  if (!m || !out) return ownError(NBL_E_BADARG, "null argument");
+  *out = nullptr;
+  void* impl = nullptr;
+  const int32_t rc = noted(m, m->v->kin_map_create(m->impl, count, kind, body, T_offset, &impl));
+  if (rc != NBL_OK) return rc;
+  *out = new nbl_kin_map{m->v, impl};
+  return NBL_OK;
+}
+void nbl_kin_map_destroy(nbl_kin_map* k) {
+  if (!k) return;
+  k->v->kin_map_destroy(k->impl);
+  delete k;
+}
+int32_t nbl_kin_map_dim(const nbl_kin_map* k) { return k ? k->v->kin_map_dim(k->impl) : 0; }
+int32_t nbl_kinematics_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, double* pos, double* vel, void* stream) {
+  if (!k) return ownError(NBL_E_BADARG, "null kinematics map");
+  if (m && k->v != m->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model");
+  return NBL_FWD(m, kinematics_forward, k->impl, B, state, pos, vel, stream);
+}
+int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* grad_pos, const double* grad_vel,
+                                double* grad_state, int32_t accumulate, void* stream) {
+  if (!k) return ownError(NBL_E_BADARG, "null kinematics map");
+  if (m && k->v != m->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model");
+  return NBL_FWD(m, kinematics_backward, k->impl, B, state, grad_pos, grad_vel, grad_state, accumulate, stream);
+}
 
 }  // extern "C"

@@ -270,6 +270,7 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
     bodies, boxes = [], []
     welded_dofs = []      # (skeleton, joint, DOFs) of every joint of an immobile skeleton: coordinates the reference's state vector has and this one does not
     ref_dof_mobile = []   # the reference World's coordinates in ITS order (skeleton by skeleton, joint by joint): True = one of this model's
+    immobile_skeletons = []   # skeleton ids (BodySpec.skeleton) of the immobile skeletons: their bodies carry no entry of an IKMapping (mapping.py)
     for sk_index, sk in enumerate(world.findall("skeleton")):
         if skeletons is not None and sk.get("name") not in skeletons:
             continue
@@ -278,6 +279,8 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
         is_mobile = mob is None or (mob.text or "").strip().lower() not in ("false", "0")   # (an empty <mobile/> reads as mobile, like the reference's default)
         if not is_mobile and immobile != "weld":
             raise ValueError(f"{path}: skeleton {sk.get('name')} is immobile (<mobile>false</mobile>); immobile=\"weld\" loads it welded to the world")
+        if not is_mobile:
+            immobile_skeletons.append(sk_index)
         bel = {b.get("name"): b for b in sk.findall("body")}
         for bn, b_ in bel.items():
             if b_.find("soft_shape") is not None:
@@ -503,6 +506,7 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
     # skeleton was welded; only the raw SoA entry points (step_soa, ...) see the device's shorter vector.
     md.welded_dofs = welded_dofs
     md.ref_dof_mobile = ref_dof_mobile if welded_dofs else None
+    md.immobile_skeletons = immobile_skeletons
     if welded_dofs:
         import warnings
         warnings.warn(f"{path}: {sum(d for _, _, d in welded_dofs)} coordinate(s) of immobile skeleton(s) "

@@ -2,7 +2,8 @@
 `BackpropSnapshot` -> `backpropState(world, nextTimestepStateLossGrad)` -> `LossGradientHighLevelAPI`
 (python/_nimblephysics/simulation_and_neural/NeuralGlobalMethods.cpp:49-53, BackpropSnapshot.cpp:59-140, NeuralUtils.cpp:58-67;
 dart/neural/NeuralUtils.cpp forwardPass, BackpropSnapshot.cpp:61-179).  Same names and argument meaning; every vector of the reference
-is a [B, .] tensor of B worlds here (a 1-D tensor is one world).  The snapshot is the saved record of nbl_step_forward."""
+is a [B, .] tensor of B worlds here (a 1-D tensor is one world).  The snapshot is the saved record of nbl_step_forward.
+`neural.IKMapping` is mapping.IKMapping (world-space body kinematics for map_to_pos / map_to_vel)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -12,6 +13,7 @@ import torch
 
 from ._lib import NimbleAmdError
 from .world import World
+from .mapping import IKMapping  # noqa: F401  (nimble.neural.IKMapping)
 
 
 class LossGradient:
