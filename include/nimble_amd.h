@@ -73,6 +73,7 @@ extern "C" {
                                         the duplicate filter's memory */
 #define NBL_ST_STANDARDIZED 0x100u /* least-squares standardized x replaced solver x (CGGM.cpp:321-332) */
 #define NBL_ST_JOINT_LIMIT 0x400u  /* >=1 joint-limit constraint row was active (dof_limit_enforced) */
+#define NBL_ST_JOINT_FRICTION 0x800u /* >=1 joint Coulomb friction row was active (coulomb_friction) */
 #define NBL_ST_GRAD_PARTIAL 0x200u /* reserved (never set: the EDGE_EDGE contact-geometry gradient terms, DCC.cpp:397-424,
                                       700-735, are evaluated by the device backward) */
 
@@ -186,6 +187,24 @@ typedef struct nbl_model_desc {
    * nbl_model_create passes the identities of the unmerged BodyNodes here (a body welded to its neighbour's child is not adjacent to it). */
   const int32_t* box_node;
   const int32_t* box_node_parent;
+
+  /* ---- joint Coulomb friction rows (appended; NULL = 0 everywhere, the reference's default: GenericJoint::mFrictions) ----
+   * [n_dofs] Joint::getCoulombFriction of the DOF, >= 0.  A DOF with f != 0 whose pre-constraint velocity (after integrateVelocities)
+   * is not exactly 0 adds one row to the LCP of its skeleton's constrained group, after the contact and the joint-limit rows
+   * (JointCoulombFrictionConstraint.cpp:110-176, ConstraintSolver.cpp:636-716): unit impulse on the DOF, b = -qdot, fixed bounds
+   * [-f dt, f dt], findex -1, no CFM (BoxedLcpConstraintSolver.cpp:291-299 asks for the velocity change without it).  Every joint type
+   * except the free-joint root (refused when such a coordinate has f != 0, as for limits).  A friction row takes one of the max_contacts
+   * contact slots (a full one: 3 rows, two of them empty), so a model with friction on k DOFs needs max_contacts >= contacts + limits + k
+   * to never drop one; such a model always runs the GENERAL instantiation of the contact stage (nbl_model_max_contacts() >= 64).  The
+   * backward pass treats a friction row as a limit row: the reference gives a non-contact constraint a zero constraint-force column
+   * (DCC.cpp:51-99), so the row drops out of every Jacobian.  Rows are recreated every step (no per-constraint warm start: mLifeTime = 0);
+   * the solver-level warm start (lcp_cache_in / out) carries them like every other row.
+   * One difference in the row set: the reference makes one constraint per JOINT that has a DOF with f != 0 (ConstraintSolver.cpp:653-661)
+   * and then activates every moving DOF of that joint (JointCoulombFrictionConstraint.cpp:107-147), so a DOF with f = 0 of such a joint
+   * gets a row with bounds [0, 0]; here only DOFs with f != 0 get rows.  The impulse of a [0, 0] row is exactly 0, so the step is the
+   * same, but for a multi-DOF joint with mixed friction (a ball joint with f = (1, 0, 0)) the row count m, the warm-start layout and the
+   * slots used are smaller than the reference's.  (Compound joints reach the library as chains of single-DOF joints.) */
+  const double* coulomb_friction;
 } nbl_model_desc;
 
 #define NBL_SHAPE_BOX 0
@@ -208,7 +227,9 @@ const char* nbl_last_error(void);
  *            instantiation of 384 rows (5.9 MB of scratch per world), the Dantzig self-test then takes n <= 384.
  *   minor 5: + nbl_set_deferred_join, nbl_slice_stream, nbl_fork_slices, nbl_join_slices (one handle, slices that are not joined per call);
  *            + nbl_kin_map_create, nbl_kin_map_destroy, nbl_kin_map_dim, nbl_kinematics_forward, nbl_kinematics_backward (world-space
- *            kinematics of body frames, below: added without a new minor number - a caller that needs them looks the symbols up). */
+ *            kinematics of body frames, below: added without a new minor number - a caller that needs them looks the symbols up);
+ *            + coulomb_friction, NBL_ST_JOINT_FRICTION (appended without a new minor number, like the kinematics entries: a library
+ *            built before the field ignores it, so a caller that depends on it checks for NBL_ST_JOINT_FRICTION in the status). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 

@@ -78,4 +78,5 @@ class ModelDesc(C.Structure):
         ("body_self_collision", _pi),
         ("box_node", _pi),
         ("box_node_parent", _pi),
+        ("coulomb_friction", _pd),
     ]

@@ -53,9 +53,12 @@ DEV GenScratch genScratchOf(double* gws, int64_t world, double* recordPinv, int 
 // are processed in tiles of `ts` (a lane = a row of the tile; the velocity-change field [body][6][ts] is what limits a tile: LDS).
 //   lds doubles: F[the model's rows][6] x 2, Sw / AISw / Vw [nb][6], psi[nb], origin[nb][3], free[nFree][54], acc[nb][6][ts], contact bodies
 // ======================================================================================================================================
-__global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const DevBody* __restrict__ bodies, const DevContactModel* __restrict__ cm, int64_t B,
-                                                         double* __restrict__ saved, SavedLayout lay, const double* __restrict__ ws, int ts) {
-  extern __shared__ __attribute__((aligned(16))) double ldsG[];
+// JF: the model has joint Coulomb friction rows (model_dev.hpp, CT_JFRIC): appended here, after the contacts and the limit rows, because
+// whether one is active depends on the pre-constraint velocity, which the narrow phase - it may run next to the forward tree kernel - has not got
+// (a body inlined into two kernels - not a kernel template: the instantiation without friction rows compiles to the kernel as it was)
+template <bool JF>
+DEV void contactRowsGen(DevModel mdl, const DevBody* __restrict__ bodies, const DevContactModel* __restrict__ cm, int64_t B,
+                        double* __restrict__ saved, SavedLayout lay, const double* __restrict__ ws, int ts, double* ldsG) {
   const int nb = mdl.nb;
   const GenWaveDev w;
   const int ln = w.lane();
@@ -72,6 +75,35 @@ __global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const Dev
   int* cbody = reinterpret_cast<int*>(acc + (size_t)6 * nb * ts);   // [2][MAX_CONTACTS]
   const int64_t b = mdl.b0 + (int64_t)blockIdx.x;
   if (b >= mdl.b1) return;
+  if (JF) {
+    // (JointCoulombFrictionConstraint::update, JointCoulombFrictionConstraint.cpp:110-149: a DOF is active iff -qdot != 0.0 exactly;
+    //  ConstraintSolver.cpp:636-716 appends the Coulomb friction constraints after the contact and joint-limit constraints.)  A row that
+    //  finds no free slot is dropped and flagged NBL_ST_CONTACT_OVERFLOW (+ 0.5 on the count, as the narrow phase does)
+    if (ln == 0) {
+      const double ncD = svAt(saved, lay.nc, B, b);
+      int nC0 = (int)ncD;
+      bool over = ncD - (double)nC0 > 0.25;
+      const DevFricModel* fm = fricModelOf(cm);
+      for (int k = 0; k < fm->nFricDofs; k++) {
+        const int d = fm->fricDof[k];
+        if (svAt(saved, lay.vpre + d, B, b) == 0.0) continue;
+        if (nC0 >= cm->maxContacts) { over = true; continue; }
+        const int r0 = lay.contacts + nC0 * CR_SIZE;
+        const int body = fm->fricBody[k];
+        for (int e = 0; e < CR_SIZE; e++) svAt(saved, r0 + e, B, b) = 0.0;
+        svAt(saved, r0 + CR_NORMAL + 1, B, b) = 1.0;                  // (a unit vector: the tangent-basis code runs on every record)
+        svAt(saved, r0 + CR_TYPE, B, b) = (double)CT_JFRIC;
+        svAt(saved, r0 + CR_BOXA, B, b) = (double)(CR_BODY_CODE + 1 + body);
+        svAt(saved, r0 + CR_BOXB, B, b) = (double)(CR_BODY_CODE + 1 + bodies[body].parent);
+        svAt(saved, r0 + CR_EA_FIXED, B, b) = (double)d;
+        svAt(saved, r0 + CR_EA_FIXED + 1, B, b) = 1.0;
+        svAt(saved, r0 + CR_EA_FIXED + 2, B, b) = fm->fricBound[k];
+        nC0++;
+      }
+      svAt(saved, lay.nc, B, b) = (double)nC0 + (over ? 0.5 : 0.0);
+    }
+    w.sync();
+  }
   const int nC = (int)svAt(saved, lay.nc, B, b);
   const int m = 3 * nC;
   if (m == 0) return;
@@ -110,7 +142,8 @@ __global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const Dev
     const V3 p = mk3(svAt(saved, r0 + CR_POINT, B, b), svAt(saved, r0 + CR_POINT + 1, B, b), svAt(saved, r0 + CR_POINT + 2, B, b));
     const V3 nrm = mk3(svAt(saved, r0 + CR_NORMAL, B, b), svAt(saved, r0 + CR_NORMAL + 1, B, b), svAt(saved, r0 + CR_NORMAL + 2, B, b));
     const int bxA = (int)svAt(saved, r0 + CR_BOXA, B, b), bxB = (int)svAt(saved, r0 + CR_BOXB, B, b);
-    const bool isLim = (int)svAt(saved, r0 + CR_TYPE, B, b) == CT_LIMIT;
+    const int type = (int)svAt(saved, r0 + CR_TYPE, B, b);
+    const bool isLim = type == CT_LIMIT || (JF && type == CT_JFRIC);   // (a friction row: the unit impulse of a limit row with sigma = +1)
     V3 t1, t2;
     tangentBasis(nrm, t1, t2);
     // a frictionless contact (mu <= 1e-3) keeps its three row slots, the two tangent rows EMPTY (k_contact_rows_coop)
@@ -147,7 +180,8 @@ __global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const Dev
     if (kk == 0) {
       // "bouncing" (ContactConstraint.cpp:393-441 / 470-512): penetration correction and restitution, see k_contact_rows_coop
       const int bxA = (int)svAt(saved, r0 + CR_BOXA, B, b), bxB = (int)svAt(saved, r0 + CR_BOXB, B, b);
-      const bool isLim = (int)svAt(saved, r0 + CR_TYPE, B, b) == CT_LIMIT;
+      const int type = (int)svAt(saved, r0 + CR_TYPE, B, b);
+      const bool isLim = type == CT_LIMIT || (JF && type == CT_JFRIC);   // (never a bounce row)
       double bouncing = 0.0;
       if (cm->penetrationCorrection && !isLim) {
         double bv = svAt(saved, r0 + CR_DEPTH, B, b) - 0.0;
@@ -164,6 +198,8 @@ __global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const Dev
       rel += bouncing;
       svAt(saved, lay.rest + ci, B, b) = coeff;
     }
+    if (JF && kk == 0 && (int)svAt(saved, r0 + CR_TYPE, B, b) == CT_JFRIC)   // b = -qdot of the DOF (JointCoulombFrictionConstraint.cpp:163)
+      rel = -svAt(saved, lay.vpre + (int)svAt(saved, r0 + CR_EA_FIXED, B, b), B, b);
     svAt(saved, lay.b + row, B, b) = rel;
   }
   w.sync();
@@ -252,6 +288,16 @@ __global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const Dev
     w.sync();
   }
 }
+__global__ __launch_bounds__(64) void k_contact_rows_gen(DevModel mdl, const DevBody* __restrict__ bodies, const DevContactModel* __restrict__ cm, int64_t B,
+                                                         double* __restrict__ saved, SavedLayout lay, const double* __restrict__ ws, int ts) {
+  extern __shared__ __attribute__((aligned(16))) double ldsG[];
+  contactRowsGen<false>(mdl, bodies, cm, B, saved, lay, ws, ts, ldsG);
+}
+__global__ __launch_bounds__(64) void k_contact_rows_gen_jf(DevModel mdl, const DevBody* __restrict__ bodies, const DevContactModel* __restrict__ cm, int64_t B,
+                                                            double* __restrict__ saved, SavedLayout lay, const double* __restrict__ ws, int ts) {
+  extern __shared__ __attribute__((aligned(16))) double ldsG[];
+  contactRowsGen<true>(mdl, bodies, cm, B, saved, lay, ws, ts, ldsG);
+}
 
 // ======================================================================================================================================
 // the solver cascade of one world
@@ -281,10 +327,10 @@ __host__ __device__ inline size_t genSolveLdsBytes(int rows) {
   return (genRowsDoubles(cap) + genFinalDoubles(cap) + GEN_SOLVE_FAST_MATS * GEN_FAST_N * GEN_FAST_N + genSolveVecDoubles(rows)) * sizeof(double);
 }
 
-__global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve_gen(DevModel mdl, const DevContactModel* __restrict__ cm, int64_t B, double* __restrict__ saved,
-                                                          SavedLayout lay, const double* __restrict__ cacheIn, double* __restrict__ cacheOut,
-                                                          double* __restrict__ next, uint32_t* __restrict__ status, double* __restrict__ gws) {
-  extern __shared__ __attribute__((aligned(16))) double ldsRows[];
+template <bool JF>
+DEV void contactSolveGen(DevModel mdl, const DevContactModel* __restrict__ cm, int64_t B, double* __restrict__ saved, SavedLayout lay,
+                         const double* __restrict__ cacheIn, double* __restrict__ cacheOut, double* __restrict__ next, uint32_t* __restrict__ status,
+                         double* __restrict__ gws, double* ldsRows) {
   const GenWaveDev w;
   const int ln = w.lane();
   const int ldr = lay.ldr;              // leading dimension of the record's dense blocks and of the world's scratch matrices
@@ -321,7 +367,7 @@ __global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve
   GEN_CNT(10);
   // ---- the rows ----
   const bool haveCache = cacheIn && ((int)cacheIn[(int64_t)MAX_ROWS * B + b] == m);
-  int nLimMine = 0;
+  int nLimMine = 0, nJfMine = 0;
   for (int r = ln; r < m; r += 64) {
     const int r0 = lay.contacts + (r / 3) * CR_SIZE;
     const int cA = (int)saved[(int64_t)(r0 + CR_BOXA) * B + b], cB = (int)saved[(int64_t)(r0 + CR_BOXB) * B + b];
@@ -332,6 +378,10 @@ __global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve
     nLimMine += lim;
     double mu = muA < muB ? muA : muB;
     if (!(mu > 1e-3)) mu = 0.0;
+    if (JF && lim && (int)saved[(int64_t)(r0 + CR_TYPE) * B + b] == CT_JFRIC) {   // the bound f dt of a joint friction row (genBoxRow)
+      mu = saved[(int64_t)(r0 + CR_EA_FIXED + 2) * B + b];
+      nJfMine++;
+    }
     R.mu[r] = mu;
     R.Bv[r] = saved[(int64_t)(lay.b + r) * B + b];
     R.fric[r] = (r % 3) != 0; R.fp[r] = r - (r % 3);
@@ -345,7 +395,10 @@ __global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve
   R.m = m; R.ld = ldr;
   const int nLim = (int)w.sumAll((double)nLimMine);
   R.anyLim = nLim > 0;
-  if (ln == 0 && status) status[b] |= (nC - nLim > 0 ? 0x1u : 0u) | (nLim > 0 ? 0x400u : 0u);
+  if (JF) {
+    const int nJf = (int)w.sumAll((double)nJfMine);
+    if (ln == 0 && status) status[b] |= (nC - nLim > 0 ? 0x1u : 0u) | (nLim - nJf > 0 ? 0x400u : 0u) | (nJf > 0 ? 0x800u : 0u);
+  } else if (ln == 0 && status) status[b] |= (nC - nLim > 0 ? 0x1u : 0u) | (nLim > 0 ? 0x400u : 0u);
   // ---- constrained groups (ConstraintSolver::buildConstrainedGroups :724-780, ContactConstraint::uniteSkeletons :879-907): skeletons
   //      connected by a contact between two reactive bodies are one group; groups are numbered by their first contact (coopGroups) ----
   if (cm->oneSkeleton) {               // (one skeleton: one constrained group - nothing to label; the labelling below is lane 0 alone)
@@ -389,12 +442,12 @@ __global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve
     GenClasses K;
     double cfmG = 0.0;
     GEN_T(0);
-    const bool ok = genStage0(w, A, ldr, R, S, haveCache, pinvValid, K);
+    const bool ok = genStage0<GenWaveDev, JF>(w, A, ldr, R, S, haveCache, pinvValid, K);
     GEN_T(1);
     if (!ok) {
       anyFail = true;
       uint32_t st = 0;
-      genCascade(w, A, ldr, R, S, cm->fallbackCfm, cfmG, st, pinvValid, K);
+      genCascade<GenWaveDev, JF>(w, A, ldr, R, S, cm->fallbackCfm, cfmG, st, pinvValid, K);
       GEN_T(12);
       stAll = (stAll & ~0x100u) | (st & ~0x100u) | (stAll & st & 0x100u);
     }
@@ -467,6 +520,18 @@ __global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve
   const bool nan = w.anyAll(bad);
   if (ln == 0 && status) status[b] |= (anyFail ? stAll : (0x2u | 0x100u)) | (nan ? 0x40u : 0u);
   GEN_T(3);
+}
+__global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve_gen(DevModel mdl, const DevContactModel* __restrict__ cm, int64_t B, double* __restrict__ saved,
+                                                          SavedLayout lay, const double* __restrict__ cacheIn, double* __restrict__ cacheOut,
+                                                          double* __restrict__ next, uint32_t* __restrict__ status, double* __restrict__ gws) {
+  extern __shared__ __attribute__((aligned(16))) double ldsRows[];
+  contactSolveGen<false>(mdl, cm, B, saved, lay, cacheIn, cacheOut, next, status, gws, ldsRows);
+}
+__global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE_GEN) void k_contact_solve_gen_jf(DevModel mdl, const DevContactModel* __restrict__ cm, int64_t B, double* __restrict__ saved,
+                                                             SavedLayout lay, const double* __restrict__ cacheIn, double* __restrict__ cacheOut,
+                                                             double* __restrict__ next, uint32_t* __restrict__ status, double* __restrict__ gws) {
+  extern __shared__ __attribute__((aligned(16))) double ldsRows[];
+  contactSolveGen<true>(mdl, cm, B, saved, lay, cacheIn, cacheOut, next, status, gws, ldsRows);
 }
 
 // ======================================================================================================================================

@@ -737,12 +737,12 @@ DEV void genMapOut(const W& w, const GenRows& R, const GenProblem& P, const doub
 }
 
 // stage 1: reduce + Dantzig with early termination (:461-522).  out: the candidate (m rows), returns GS_* flags
-template <class W>
+template <class W, bool JF = false>
 DEV int genStage1(const W& w, const double* A, int lda, GenRows& R, const GenScratch& S, double* out) {
   GenProblem P; GenDantzigMem D;
   GEN_T0();
   genCarve(S, P, D, R.m);
-  genLoadProblem(w, A, lda, R, 0.0, R.X0, P);
+  genLoadProblem<W, JF>(w, A, lda, R, 0.0, R.X0, P);
   genLcpReduce(w, R, P, R.m);
   GEN_T(4);
   int rc;
@@ -769,17 +769,17 @@ DEV int genStage1(const W& w, const double* A, int lda, GenRows& R, const GenScr
   w.sync();
   if (rc == 1) {
     genMapOut(w, R, P, P.x, out);
-    flags = GS_SOLVED | (genValid(w, A, lda, R, out, false, 0.0, R.t2) ? GS_VALID : 0);
+    flags = GS_SOLVED | (genValid<W, JF>(w, A, lda, R, out, false, 0.0, R.t2) ? GS_VALID : 0);
   } else if (rc < 0) flags = GS_NAN;
   GEN_T(6);
   return flags;
 }
 // stage 2: CFM + reduce + PGS from the pre-solve x (:539-597)
-template <class W>
+template <class W, bool JF = false>
 DEV int genStage2(const W& w, const double* A, int lda, GenRows& R, const GenScratch& S, double cfm, double* out) {
   GenProblem P; GenDantzigMem D;
   genCarve(S, P, D, R.m);
-  genLoadProblem(w, A, lda, R, cfm, R.X0, P);
+  genLoadProblem<W, JF>(w, A, lda, R, cfm, R.X0, P);
   genLcpReduce(w, R, P, R.m);
   int flags = 0;
   for (int r = w.lane(); r < R.m; r += w.lanes()) out[r] = 0.0;
@@ -787,16 +787,16 @@ DEV int genStage2(const W& w, const double* A, int lda, GenRows& R, const GenScr
   const GenPgsAT at = genPgsAT(S, P.n, R.m);
   if (genPgs(w, R, P, at.AT, at.ld, at.lds)) {
     genMapOut(w, R, P, P.x, out);
-    flags = GS_SOLVED | (genValid(w, A, lda, R, out, false, cfm, R.t2) ? GS_VALID : 0);
+    flags = GS_SOLVED | (genValid<W, JF>(w, A, lda, R, out, false, cfm, R.t2) ? GS_VALID : 0);
   }
   return flags;
 }
 // stage 3: drop friction, PGS from zero (:606-677); its result is used whatever the solver says
-template <class W>
+template <class W, bool JF = false>
 DEV int genStage3(const W& w, const double* A, int lda, GenRows& R, const GenScratch& S, double cfm, double* out) {
   GenProblem P; GenDantzigMem D;
   genCarve(S, P, D, R.m);
-  genLoadProblem(w, A, lda, R, cfm, R.X0, P);
+  genLoadProblem<W, JF>(w, A, lda, R, cfm, R.X0, P);
   genLcpRemoveFriction(w, R, P, R.m, S.mat[1]);
   for (int c = w.lane(); c < P.n; c += w.lanes()) P.x[c] = 0.0;
   w.sync();
@@ -809,7 +809,7 @@ DEV int genStage3(const W& w, const double* A, int lda, GenRows& R, const GenScr
 // The cascade for the rows that are on: the stages in the reference's order of preference (a later stage only runs when the earlier ones
 // did not deliver), then registration, classification and standardisation of the chosen solution (:718-736).  R.X0: the pre-solve x;
 // out: R.X (impulses), R.cls / R.E, cfmOut, st (NBL_ST_* bits), pinvValid (S.mat[3] is Q^+ of the classification).
-template <class W>
+template <class W, bool JF = false>
 DEV void genCascade(const W& w, const double* A, int lda, GenRows& R, const GenScratch& S, double fallbackCfm, double& cfmOut, uint32_t& stOut,
                     bool& pinvValid, GenClasses& K) {
   const int m = R.m;
@@ -821,7 +821,7 @@ DEV void genCascade(const W& w, const double* A, int lda, GenRows& R, const GenS
   double cfm = 0.0;
   take(R.X0);
   GEN_CNT(11);
-  const int f1 = genStage1(w, A, lda, R, S, cand);
+  const int f1 = genStage1<W, JF>(w, A, lda, R, S, cand);
   GEN_T0();
   if (f1 & GS_SOLVED) {
     take(cand);
@@ -831,7 +831,7 @@ DEV void genCascade(const W& w, const double* A, int lda, GenRows& R, const GenS
   if ((f1 & GS_NAN) || hasNan(R.X)) { success = false; for (int r = w.lane(); r < m; r += w.lanes()) R.X[r] = 0.0; w.sync(); st |= 0x40u; }
   if (!success) {
     cfm = fallbackCfm;
-    const int f2 = genStage2(w, A, lda, R, S, fallbackCfm, cand);
+    const int f2 = genStage2<W, JF>(w, A, lda, R, S, fallbackCfm, cand);
     if (f2 & GS_SOLVED) {
       take(cand);
       success = (f2 & GS_VALID) != 0;
@@ -841,7 +841,7 @@ DEV void genCascade(const W& w, const double* A, int lda, GenRows& R, const GenS
   GEN_T(7);
   if (!success) {
     ignoreFriction = true;
-    const int f3 = genStage3(w, A, lda, R, S, fallbackCfm, cand);
+    const int f3 = genStage3<W, JF>(w, A, lda, R, S, fallbackCfm, cand);
     take(cand);
     st |= 0x10u;
     if (!(f3 & GS_SOLVED)) st |= 0x20u;
@@ -849,7 +849,7 @@ DEV void genCascade(const W& w, const double* A, int lda, GenRows& R, const GenS
   if (hasNan(R.X)) { for (int r = w.lane(); r < m; r += w.lanes()) R.X[r] = 0.0; w.sync(); st |= 0x40u; }
   pinvValid = false;
   GEN_T(8);
-  const bool std = genStandardizeLoop(w, A, lda, R, S, cfm, ignoreFriction, nullptr, pinvValid, K);
+  const bool std = genStandardizeLoop<W, JF>(w, A, lda, R, S, cfm, ignoreFriction, nullptr, pinvValid, K);
   GEN_T(9);
   if (std) st |= 0x100u;
   cfmOut = cfm; stOut = st;

@@ -136,8 +136,18 @@ DEV void genAx(const W& w, const double* A, int lda, const GenRows& R, const dou
   w.sync();
 }
 
+// JF: the model has joint Coulomb friction rows (model_dev.hpp, CT_JFRIC) - the normal row of a joint pseudo-contact (R.lim) that carries
+// mu = f dt > 0 is a row with the FIXED bounds [-f dt, f dt] and findex -1 (JointCoulombFrictionConstraint::getInformation,
+// JointCoulombFrictionConstraint.cpp:152-176).  Only the instantiation for such models compiles the test (JF = false: the code as before).
+template <bool JF>
+DEV bool genBoxRow(const GenRows& R, int r) { return JF && R.lim[r] && R.mu[r] > 0.0; }
+template <bool JF>
+DEV double genRowHi(const GenRows& R, int r) { return (R.fric[r] || genBoxRow<JF>(R, r)) ? R.mu[r] : INFINITY; }
+template <bool JF>
+DEV double genRowLo(const GenRows& R, int r) { return (R.fric[r] || genBoxRow<JF>(R, r)) ? -R.mu[r] : 0.0; }
+
 // LCPUtils::isLCPSolutionValid (LCPUtils.cpp:12-80) on the rows that are on; v: scratch of m doubles.  Uniform result.
-template <class W>
+template <class W, bool JF = false>
 DEV bool genValid(const W& w, const double* A, int lda, const GenRows& R, const double* X, bool ignoreFriction, double cfm, double* v) {
   const double tol = 1e-5;
   genAx(w, A, lda, R, X, v);
@@ -146,7 +156,7 @@ DEV bool genValid(const W& w, const double* A, int lda, const GenRows& R, const 
     if (!R.on[r]) continue;
     const double x = X[r];
     const double vr = -R.Bv[r] + cfm * x + v[r];
-    double upper = R.fric[r] ? R.mu[r] : INFINITY, lower = R.fric[r] ? -R.mu[r] : 0.0;
+    double upper = genRowHi<JF>(R, r), lower = genRowLo<JF>(R, r);
     if (R.fric[r]) {
       if (ignoreFriction) { if (x != 0.0) bad = true; continue; }
       const double xn = R.on[R.fp[r]] ? X[R.fp[r]] : 0.0;
@@ -166,17 +176,18 @@ DEV bool genValid(const W& w, const double* A, int lda, const GenRows& R, const 
 struct GenClasses { int nc, nu; };
 
 // CGGM::constructMatrices classification (CGGM.cpp:535-713) of the rows that are on -> R.cls, R.E
-template <class W>
+template <class W, bool JF = false>
 DEV GenClasses genClassify(const W& w, GenRows& R, const double* X, bool ignoreFriction) {
   const double TH = 1e-6, tie = 1e-5;
   const int m = R.m;
-  // pass 1: clamping or not (a friction row looks at the impulse of its normal row, not at its class)
+  // pass 1: clamping or not (a friction row looks at the impulse of its normal row, not at its class; a row with fixed bounds, JF, is
+  // clamping strictly inside them and not clamping on them, CGGM.cpp:560-715)
   for (int r = w.lane(); r < m; r += w.lanes()) {
     int cls = RC_NOT_CLAMPING;
     bool inElse = false;
     const double x = R.on[r] ? X[r] : 0.0;
     const double xn = R.on[R.fp[r]] ? X[R.fp[r]] : 0.0;
-    const double hi = R.fric[r] ? R.mu[r] : INFINITY, lo = R.fric[r] ? -R.mu[r] : 0.0;
+    const double hi = genRowHi<JF>(R, r), lo = genRowLo<JF>(R, r);
     double upper = hi, lower = lo;
     if (R.fric[r]) { upper *= xn; lower *= xn; }
     if (R.on[r] && !(R.colNorm[r] < 1e-9)) {
@@ -468,7 +479,7 @@ constexpr int GEN_FAST_DOUBLES = GEN_FAST_MATS * GEN_FAST_N * GEN_FAST_N + 20 * 
 // CGGM::constructMatrices + opportunisticallyStandardizeResults as a loop (coopStandardizeLoop of coop_dev.hpp).  X in: the solver's x
 // (R.X), out: the last accepted solution.  guessValid: S.mat[3] holds the pseudo-inverse of A restricted to the rows R.in0 (stage 0's
 // guess).  Returns whether the results are standardised; pinvValid: S.mat[3] is Q^+ of the classification in R.cls.
-template <class W>
+template <class W, bool JF = false>
 DEV bool genStandardizeLoop(const W& w, const double* A, int lda, GenRows& R, const GenScratch& S, double cfm, bool ignoreFriction,
                             const unsigned char* guessRows, bool& pinvValid, GenClasses& K) {
   const int m = R.m;
@@ -479,13 +490,13 @@ DEV bool genStandardizeLoop(const W& w, const double* A, int lda, GenRows& R, co
   GEN_L0();
   for (int iter = 0; iter < m + 1; iter++) {
     GEN_CNT(24);
-    K = genClassify(w, R, X, ignoreFriction);
+    K = genClassify<W, JF>(w, R, X, ignoreFriction);
     GEN_L(19);
     if (K.nc == 0) {
       pinvValid = false;
       for (int r = w.lane(); r < m; r += w.lanes()) newX[r] = 0.0;
       w.sync();
-      ok = genValid(w, A, lda, R, newX, ignoreFriction, cfm, R.t2);
+      ok = genValid<W, JF>(w, A, lda, R, newX, ignoreFriction, cfm, R.t2);
       if (ok) { for (int r = w.lane(); r < m; r += w.lanes()) X[r] = 0.0; w.sync(); }
       break;
     }
@@ -525,7 +536,7 @@ DEV bool genStandardizeLoop(const W& w, const double* A, int lda, GenRows& R, co
     w.sync();
     const bool again = w.anyAll(newlyNot);
     GEN_L(22);
-    const bool valid_ = genValid(w, A, lda, R, newX, ignoreFriction, cfm, R.t2);
+    const bool valid_ = genValid<W, JF>(w, A, lda, R, newX, ignoreFriction, cfm, R.t2);
     GEN_L(23);
     if (!valid_) { ok = false; break; }
     for (int r = w.lane(); r < m; r += w.lanes()) X[r] = newX[r];
@@ -539,7 +550,7 @@ DEV bool genStandardizeLoop(const W& w, const double* A, int lda, GenRows& R, co
 
 // LCPUtils::guessSolution (when there is no matching warm start) + the standardisation loop: stage 0 of the solver cascade
 // (BoxedLcpConstraintSolver.cpp:380-460).  R.X in: the warm start (haveCache), out: the solution; R.X0: the pre-solve x.
-template <class W>
+template <class W, bool JF = false>
 DEV bool genStage0(const W& w, const double* A, int lda, GenRows& R, const GenScratch& S, bool haveCache, bool& pinvValid, GenClasses& K) {
   const int ld = R.ld;              // leading dimension of the scratch matrices (the model's rows, rounded up)
   const int m = R.m;
@@ -582,7 +593,7 @@ DEV bool genStage0(const W& w, const double* A, int lda, GenRows& R, const GenSc
   for (int r = w.lane(); r < m; r += w.lanes()) R.X0[r] = R.X[r];
   w.sync();
   GEN_L(18);
-  const bool ok = genStandardizeLoop(w, A, lda, R, S, 0.0, false, haveGuess ? in0 : nullptr, pinvValid, K);
+  const bool ok = genStandardizeLoop<W, JF>(w, A, lda, R, S, 0.0, false, haveGuess ? in0 : nullptr, pinvValid, K);
   pinvValid = ok && pinvValid;
   return ok;
 }
@@ -596,7 +607,7 @@ struct GenProblem {          // compacted boxed LCP (arrays in the world's scrat
 
 // A (+ cfm on the diagonal) restricted to the rows the reference's problem has: rows that are on, without the empty tangent rows of
 // frictionless contacts (ContactConstraint dimension 1).  Lane 0 compacts the indices, the lanes copy.
-template <class W>
+template <class W, bool JF = false>
 DEV void genLoadProblem(const W& w, const double* A, int lda, GenRows& R, double cfmDiag, const double* x0, GenProblem& P) {
   const int ld = R.ld;              // leading dimension of the scratch matrices (the model's rows, rounded up)
   const int m = R.m;
@@ -611,7 +622,7 @@ DEV void genLoadProblem(const W& w, const double* A, int lda, GenRows& R, double
       const int c = P.mapTo[r];
       if (c < 0) continue;
       P.x[c] = x0[r]; P.b[c] = R.Bv[r];
-      P.lo[c] = R.fric[r] ? -R.mu[r] : 0.0; P.hi[c] = R.fric[r] ? R.mu[r] : INFINITY;
+      P.lo[c] = genRowLo<JF>(R, r); P.hi[c] = genRowHi<JF>(R, r);
       P.findex[c] = R.fric[r] ? P.mapTo[R.fp[r]] : -1;
     }
     R.iscal[0] = n;

@@ -183,11 +183,25 @@ struct DevContactModel {
   int32_t limitDof[MAX_DOF_CONTACT], limitBody[MAX_DOF_CONTACT];
   double limitLo[MAX_DOF_CONTACT], limitHi[MAX_DOF_CONTACT];
 };
+// joint Coulomb friction rows (JointCoulombFrictionConstraint.cpp; nbl_model_desc.coulomb_friction; general instantiation only): the DOFs with a
+// non-zero friction force f, their device body and the bound f dt.  A moving one becomes a pseudo-contact (CT_JFRIC) after the limit rows.
+// Stored in the same device allocation right BEHIND the DevContactModel of a general build (fricModelOf), so that the collider model every
+// other kernel reads - the narrow phase copies it to LDS - keeps its size.
+struct DevFricModel {
+  int32_t nFricDofs, pad_;
+  int32_t fricDof[MAX_DOF_CONTACT], fricBody[MAX_DOF_CONTACT];
+  double fricBound[MAX_DOF_CONTACT];
+};
+__device__ __forceinline__ const DevFricModel* fricModelOf(const DevContactModel* cm) { return reinterpret_cast<const DevFricModel*>(cm + 1); }
 // A joint-limit row in the contact record: type CT_LIMIT, the two "colliders" are the codes CR_BODY_CODE + 1 + body of the joint's child
 // body (A) and of its parent body (B; world = -1), CR_EA_FIXED = (DOF, sigma, 0).  sigma = +1 at the lower limit; at the upper limit the
 // row is carried NEGATED (sigma = -1: x' = -x >= 0, row and column of A and b negated - exact in IEEE arithmetic) so that every stage sees
 // a frictionless normal row with bounds [0, inf); the warm-start cache and LCPUtils::guessSolution's `b > 0` use the reference's sign.
 constexpr int CT_LIMIT = 30, CR_BODY_CODE = 64;
+// A joint Coulomb friction row: type CT_JFRIC, colliders as a limit row's, CR_EA_FIXED = (DOF, +1, f dt).  Every stage sees it as a
+// row with the fixed bounds [-f dt, f dt] and findex -1 (the normal row of the record with mu = f dt; gen_lcp_dev.hpp, JF); the backward
+// pass treats it as a limit row (zero constraint-force column, DCC.cpp:51-99).
+constexpr int CT_JFRIC = 31;
 __device__ __forceinline__ int crBodyOf(const DevContactModel* __restrict__ cm, int code) { return code >= CR_BODY_CODE ? code - CR_BODY_CODE - 1 : cm->boxes[code].body; }
 __device__ __forceinline__ double crMuOf(const DevContactModel* __restrict__ cm, int code) { return code >= CR_BODY_CODE ? 0.0 : cm->boxes[code].mu; }
 

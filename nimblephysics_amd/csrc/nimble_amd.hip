@@ -92,6 +92,7 @@ struct nbl_model {
   int rowsPack = 1;                  // worlds per wavefront of k_contact_rows_coop (2: the 24-row build, <= 32 device bodies; NBL_ROWS_PACK=1 forces 1)
   int nPairs = 0;                    // candidate collider pairs of the model
   bool multiGroup = false;           // colliders on more than one skeleton: a world can hold several constrained groups
+  bool jointFriction = false;        // joint Coulomb friction rows (general instantiation: the _jf kernels of gen_contact.hip)
   bool coopFinal = true;             // the backward sweeps too, in the world frame (NBL_COOP_FINAL=0: one world per lane, fed by k_tree_to_lanes)
   bool coopTree = false;             // tree sweeps one world per wavefront (needs the saved tree block, nb and n <= 64)
   int treeLanes = 0;                 // worlds per workgroup of the one-world-per-lane tree kernels (0 = pick from B); nbl_set_launch_lanes
@@ -391,6 +392,8 @@ int32_t nbl_model_create(const nbl_model_desc* d, int32_t device, nbl_model** ou
   // ---- contact model: box colliders, candidate pairs (CollisionFilter.cpp:105-154), ancestor masks ----
   DevContactModel hc;
   std::memset(&hc, 0, sizeof(hc));
+  DevFricModel hf;                     // (general builds: uploaded behind hc, fricModelOf)
+  std::memset(&hf, 0, sizeof(hf));
   // joint-limit constraint rows (dof_limit_enforced): the joints with a finite limit to enforce, one entry per DOF (= per device body)
   std::vector<int> limitDofs;
   if (d->dof_limit_enforced)
@@ -413,7 +416,29 @@ int32_t nbl_model_create(const nbl_model_desc* d, int32_t device, nbl_model** ou
     }
   if (!limitDofs.empty() && d->max_contacts <= 0)
     return fail(NBL_E_BADARG, "dof_limit_enforced needs max_contacts > 0: a joint-limit row takes one contact slot of the LCP");
-  bool hasContact = (d->n_boxes > 0 || !limitDofs.empty()) && d->max_contacts > 0;
+  // joint Coulomb friction rows (coulomb_friction): the DOFs with f != 0, one entry per DOF (= per device body), in DOF order - the order of
+  // the reference's constraints within a skeleton (joint by joint, DOF by DOF), as for the limit rows
+  std::vector<int> fricDofs;
+  if (d->coulomb_friction)
+    for (int i = 0; i < d->n_bodies; i++) {
+      const int jt = d->joint_type[i];
+      if (jt == NBL_JOINT_WELD) continue;
+      const int nd = jt == NBL_JOINT_FREE ? 6 : 1;
+      for (int k = 0; k < nd; k++) {
+        const double f = d->coulomb_friction[d->dof_offset[i] + k];
+        if (!(f >= 0.0) || !std::isfinite(f)) return fail(NBL_E_BADARG, "coulomb_friction must be finite and >= 0");
+        if (jt == NBL_JOINT_FREE && f != 0.0)   // (solved in its body frame, like its limits: no rows for its coordinates)
+          return fail(NBL_E_UNSUPPORTED, "coulomb_friction on the coordinates of a free-joint root");
+      }
+      if (jt != NBL_JOINT_FREE && d->coulomb_friction[d->dof_offset[i]] != 0.0) fricDofs.push_back(i);
+    }
+  if (!fricDofs.empty() && d->max_contacts <= 0)
+    return fail(NBL_E_BADARG, "coulomb_friction needs max_contacts > 0: a joint friction row takes one contact slot of the LCP");
+#if !NBL_GENERAL
+  // (the lane = row instantiations have no rows with fixed bounds: the general one takes the model)
+  if (!fricDofs.empty()) return fail(NBL_E_CAPACITY, "joint Coulomb friction rows run on the general instantiation of the contact stage");
+#endif
+  bool hasContact = (d->n_boxes > 0 || !limitDofs.empty() || !fricDofs.empty()) && d->max_contacts > 0;
   bool multiGroupModel = !limitDofs.empty();   // the general instantiation of the contact kernels carries the joint-limit rows
   if (hasContact) {
     // (NBL_E_CAPACITY: the 24-row build hands such a model on to the 48-row build, nimble_amd_dispatch.cpp; from that one it is final)
@@ -426,6 +451,11 @@ int32_t nbl_model_create(const nbl_model_desc* d, int32_t device, nbl_model** ou
     for (int k = 0; k < hc.nLimitDofs; k++) {
       const int body = limitDofs[k], j = d->dof_offset[body];
       hc.limitDof[k] = j; hc.limitBody[k] = body; hc.limitLo[k] = hd[j].posLo; hc.limitHi[k] = hd[j].posHi;
+    }
+    hf.nFricDofs = (int)fricDofs.size();
+    for (int k = 0; k < hf.nFricDofs; k++) {
+      const int body = fricDofs[k], j = d->dof_offset[body];
+      hf.fricDof[k] = j; hf.fricBody[k] = body; hf.fricBound[k] = d->coulomb_friction[j] * d->dt;   // (JointCoulombFrictionConstraint.cpp:129)
     }
     hc.maxContacts = d->max_contacts;
     hc.clippingDepth = d->contact_clipping_depth;
@@ -512,6 +542,7 @@ int32_t nbl_model_create(const nbl_model_desc* d, int32_t device, nbl_model** ou
   nbl_model* m = new nbl_model();
   m->hasContact = hasContact;
   m->multiGroup = multiGroupModel;
+  m->jointFriction = !fricDofs.empty();
   {
     SavedLayout& L = m->lay;
     const int n = d->n_dofs;
@@ -624,13 +655,16 @@ int32_t nbl_model_create(const nbl_model_desc* d, int32_t device, nbl_model** ou
   m->hBodies = hb;
   if (e == hipSuccess) e = hipMemcpy(m->dBodies, hb.data(), sizeof(DevBody) * hb.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->dDofs, hd.data(), sizeof(DevDof) * hd.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess && hasContact) e = hipMalloc((void**)&m->dContact, sizeof(DevContactModel));
+  const size_t fricBytes = NBL_GENERAL ? sizeof(DevFricModel) : 0;   // (the friction rows' constants right behind the collider model)
+  if (e == hipSuccess && hasContact) e = hipMalloc((void**)&m->dContact, sizeof(DevContactModel) + fricBytes);
   if (e == hipSuccess && hasContact) e = hipMemcpy(m->dContact, &hc, sizeof(DevContactModel), hipMemcpyHostToDevice);
+  if (e == hipSuccess && hasContact && fricBytes) e = hipMemcpy(m->dContact + 1, &hf, fricBytes, hipMemcpyHostToDevice);
   // (k_contact_detect: 160 kB less its static arrays - the remembered points and the clip polygons)
   if (e == hipSuccess && hasContact) e = hipFuncSetAttribute((const void*)k_contact_detect, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                              std::min(104 * 1024, 160 * 1024 - (SEEN_POINTS * 3 * DETECT_LS + 48 * DETECT_LS) * (int)sizeof(double)));
 #if NBL_GENERAL
   if (e == hipSuccess && hasContact) e = hipFuncSetAttribute((const void*)k_contact_rows_gen, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e == hipSuccess && hasContact) e = hipFuncSetAttribute((const void*)k_contact_rows_gen_jf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e == hipSuccess && hasContact) e = hipFuncSetAttribute((const void*)k_bwd_contact_b_gen<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e == hipSuccess && hasContact) e = hipFuncSetAttribute((const void*)k_bwd_contact_b_gen<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #else
@@ -795,9 +829,10 @@ static int32_t launchForward(nbl_model* m, int64_t B, int si, int64_t b0, int64_
         while (ts > 8 && rowsLdsFor(ts) > 150u * 1024u) ts /= 2;
         while (ts > 32 && (ts / 2 >= ldrRows || rowsLdsFor(ts) > 48u * 1024u)) ts /= 2;
         if (const char* e = getenv("NBL_ROWS_TS")) { const int t = atoi(e); if (t >= 8 && t <= 64 && rowsLdsFor(t) <= 150u * 1024u) ts = t; }
-        TIMED(K_ROWS_COOP, hipLaunchKernelGGL(k_contact_rows_gen, dim3((unsigned)cnt), dim3(64), rowsLdsFor(ts), s, mdl, m->dBodies, m->dContact, B,
+        const bool jf = m->jointFriction;
+        TIMED(K_ROWS_COOP, hipLaunchKernelGGL(jf ? k_contact_rows_gen_jf : k_contact_rows_gen, dim3((unsigned)cnt), dim3(64), rowsLdsFor(ts), s, mdl, m->dBodies, m->dContact, B,
                                               (double*)saved, m->lay, (const double*)workspace, ts));
-        TIMED(K_SOLVE_COOP, hipLaunchKernelGGL(k_contact_solve_gen, dim3((unsigned)cnt), dim3(64), genSolveLdsBytes(m->lay.ldr), s, mdl, m->dContact, B, (double*)saved, m->lay,
+        TIMED(K_SOLVE_COOP, hipLaunchKernelGGL(jf ? k_contact_solve_gen_jf : k_contact_solve_gen, dim3((unsigned)cnt), dim3(64), genSolveLdsBytes(m->lay.ldr), s, mdl, m->dContact, B, (double*)saved, m->lay,
                                                lcp_cache_in, lcp_cache_out, next_state, status, gws));
       }
       (void)lws; (void)failListAll;

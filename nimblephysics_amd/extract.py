@@ -42,6 +42,13 @@ def _mat4(T) -> np.ndarray:
     return np.asarray(M, dtype=np.float64).reshape(4, 4)
 
 
+def _friction(j, nd):
+    if not hasattr(j, "getCoulombFriction"):
+        return ()
+    f = tuple(float(j.getCoulombFriction(k)) for k in range(nd))
+    return f if any(f) else ()
+
+
 def _limit(v, lo: bool):
     v = float(v)
     return v if np.isfinite(v) else (-np.inf if lo else np.inf)
@@ -100,7 +107,9 @@ def model_from_nimble_world(world, name: str = "extracted", max_contacts: Option
                             force_lo=tuple(_limit(j.getControlForceLowerLimit(k), True) for k in range(nd)),
                             force_hi=tuple(_limit(j.getControlForceUpperLimit(k), False) for k in range(nd)),
                             # Joint::isPositionLimitEnforced (python/_nimblephysics/dynamics/Joint.cpp:202): joint-limit LCP rows
-                            limit_enforced=bool(j.isPositionLimitEnforced()) if hasattr(j, "isPositionLimitEnforced") else False)
+                            limit_enforced=bool(j.isPositionLimitEnforced()) if hasattr(j, "isPositionLimitEnforced") else False,
+                            # Joint::getCoulombFriction: joint Coulomb friction LCP rows (omitted - all zero - when the joint does not offer it)
+                            coulomb_friction=_friction(j, nd))
             if jt in _COMPOUND_TYPES:
                 # expanded into 1-DOF chains by ModelDescription (model.py); only the axes differ per class
                 kw = per_dof()
@@ -125,7 +134,7 @@ def model_from_nimble_world(world, name: str = "extracted", max_contacts: Option
                     if jtype == "screw":
                         kw["pitch"] = float(j.getPitch())
                 elif jtype == "free":
-                    kw = {k_: v for k_, v in per_dof().items() if k_ in ("damping", "spring", "rest")}
+                    kw = {k_: v for k_, v in per_dof().items() if k_ in ("damping", "spring", "rest", "coulomb_friction")}
                 elif jtype == "ball":
                     kw = per_dof()
             m = inertia_of[(si, bi)]

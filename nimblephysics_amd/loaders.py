@@ -9,7 +9,7 @@ Conventions follow the reference's dart/utils/urdf/DartLoader.cpp (parameters on
     from it), which fixes the DOF order of the skeleton
   * collision boxes -> box colliders with the collision origin as the shape's relative transform (:612-616);
     mesh / capsule / cylinder colliders (libccd path, not vendored) raise, or are dropped on request
-Revolute, continuous, prismatic, fixed, floating and planar joints (every type DartLoader::createDartJoint knows); joint Coulomb friction raises.
+Revolute, continuous, prismatic, fixed, floating and planar joints (every type DartLoader::createDartJoint knows); joint Coulomb friction (`<dynamics friction=...>`) is read into BodySpec.coulomb_friction.
 """
 import os
 import xml.etree.ElementTree as ET
@@ -117,7 +117,7 @@ def load_urdf(path, name=None, weld_joints=(), drop_unsupported_colliders=False)
                 if dyn is not None:
                     kw["damping"] = (float(dyn.get("damping", 0.0)),)
                     if float(dyn.get("friction", 0.0)) != 0.0:
-                        raise ValueError(f"{jn}: joint Coulomb friction is outside the hot-path scope")
+                        kw["coulomb_friction"] = (float(dyn.get("friction")),)   # DartLoader.cpp:436
                 axis = _floats(j.find("axis").get("xyz")) if j.find("axis") is not None else [1, 0, 0]
             elif jt == "fixed" or jn in weld_joints:
                 jtype, axis = "weld", [0, 0, 1]
@@ -375,7 +375,8 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
                     """damping / spring / rest / limits of <axis>, <axis2>, ... (readJointDynamicsAndLimit, :1870-1960): per-DOF
                     lists of length k with the reference's defaults where an element is missing."""
                     inf = float("inf")
-                    P = {"damping": [0.0] * k, "spring": [0.0] * k, "rest": [0.0] * k, "pos_lo": [-inf] * k, "pos_hi": [inf] * k}
+                    P = {"damping": [0.0] * k, "spring": [0.0] * k, "rest": [0.0] * k, "pos_lo": [-inf] * k, "pos_hi": [inf] * k,
+                         "coulomb_friction": [0.0] * k}
                     for i in range(k):
                         ax = j.find("axis" if i == 0 else f"axis{i + 1}")
                         if ax is None:
@@ -384,8 +385,7 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
                         dyn = ax.find("dynamics")
                         if dyn is not None:
                             damp = _text(dyn, "damping", damp)
-                            if _text(dyn, "friction", 0.0) != 0.0:
-                                raise ValueError(f"{j.get('name')}: joint Coulomb friction is outside the hot-path scope")
+                            P["coulomb_friction"][i] = _text(dyn, "friction", 0.0)   # (SkelParser.cpp:1921-1925)
                             P["spring"][i] = _text(dyn, "spring_stiffness", 0.0)
                             P["rest"][i] = _text(dyn, "spring_rest_position", 0.0)
                         if damp is not None:
@@ -394,7 +394,7 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
                         if lim is not None:
                             P["pos_lo"][i] = _text(lim, "lower", -inf)
                             P["pos_hi"][i] = _text(lim, "upper", inf)
-                    dflt = {"damping": 0.0, "spring": 0.0, "rest": 0.0, "pos_lo": -inf, "pos_hi": inf}
+                    dflt = {"damping": 0.0, "spring": 0.0, "rest": 0.0, "pos_lo": -inf, "pos_hi": inf, "coulomb_friction": 0.0}
                     return {key: tuple(v) for key, v in P.items() if any(x != dflt[key] for x in v)}   # all-default: leave unset
 
                 def plane_axes():
@@ -452,7 +452,7 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
                 if dofs and ndofs > 0:
                     inf = float("inf")
                     dflt = {"damping": 0.0, "spring": 0.0, "rest": 0.0, "pos_lo": -inf, "pos_hi": inf, "vel_lo": -inf, "vel_hi": inf,
-                            "force_lo": -inf, "force_hi": inf}
+                            "force_lo": -inf, "force_hi": inf, "coulomb_friction": 0.0}
                     P = {key: list(kw.get(key, ())) or [dflt[key]] * ndofs for key in dflt}
                     for de in dofs:
                         li = de.get("local_index")
@@ -473,8 +473,8 @@ def load_skel(path, name=None, skeletons=None, max_contacts=None, drop_unsupport
                         for tag, key in (("damping", "damping"), ("spring_rest_position", "rest"), ("spring_stiffness", "spring")):
                             if de.find(tag) is not None:
                                 P[key][li] = float(de.find(tag).text)
-                        if de.find("friction") is not None and float(de.find("friction").text) != 0.0:
-                            raise ValueError(f"{j.get('name')}: joint Coulomb friction is outside the hot-path scope")
+                        if de.find("friction") is not None:                # (SkelParser.cpp:1858-1859)
+                            P["coulomb_friction"][li] = float(de.find("friction").text)
                     for key, vals in P.items():
                         if any(x != dflt[key] for x in vals):
                             kw[key] = tuple(vals)

@@ -93,6 +93,7 @@ class BodySpec:
     axes: Sequence[Sequence[float]] = ()   # compound joints with free axes (universal: 2, translational2d: 2, planar: 2 in-plane axes)
     beta: Sequence[float] = (1.0, 1.0, 1.0)   # BodyNode::mBeta (BodyNode.cpp:1301 ctor default ones): the COM moves along beta under an INERTIA_COM_MU mass entry
     limit_enforced: bool = False   # Joint::isPositionLimitEnforced (JointAspect.hpp:165: off by default): the joint's position limits become LCP rows
+    coulomb_friction: Sequence[float] = ()   # per DOF, Joint::getCoulombFriction (default 0): a moving DOF gets an LCP row with bounds +- f dt
     self_collision: bool = False        # Skeleton::isEnabledSelfCollisionCheck of the body's skeleton (off by default): colliders of one skeleton meet
     adjacent_body_check: bool = False   # Skeleton::isEnabledAdjacentBodyCheck: ... also those of a body and its parent
     skeleton: int = -1   # index of the dart Skeleton the body belongs to; -1 (every body of the model) = one skeleton per tree
@@ -163,7 +164,7 @@ def expand_compound_joints(bodies, boxes):
                 T_pj=np.array(b.T_pj, dtype=np.float64) if i == 0 else np.eye(4), T_cj=np.array(b.T_cj, dtype=np.float64) if last else np.eye(4),
                 mass=b.mass if last else 0.0, com=tuple(b.com) if last else (0.0, 0.0, 0.0),
                 inertia=tuple(b.inertia) if last else (0.0,) * 6,
-                **{key: dof(getattr(b, key), i) for key in ("damping", "spring", "rest", "pos_lo", "pos_hi", "vel_lo", "vel_hi", "force_lo", "force_hi")},
+                **{key: dof(getattr(b, key), i) for key in ("damping", "spring", "rest", "pos_lo", "pos_hi", "vel_lo", "vel_hi", "force_lo", "force_hi", "coulomb_friction")},
                 friction=b.friction, beta=tuple(b.beta) if last else (1.0, 1.0, 1.0), limit_enforced=b.limit_enforced, self_collision=b.self_collision, adjacent_body_check=b.adjacent_body_check, skeleton=b.skeleton)
             parent = len(out)
             out.append(nb)
@@ -390,7 +391,7 @@ class ModelDescription:
             "com": np.zeros((nb, 3)), "inertia": np.zeros((nb, 6)),
             "damping": np.zeros(n), "spring": np.zeros(n), "rest": np.zeros(n), "dof_limit_enforced": np.zeros(n, np.int32),
             "pos_lo": np.full(n, -inf), "pos_hi": np.full(n, inf), "vel_lo": np.full(n, -inf), "vel_hi": np.full(n, inf),
-            "force_lo": np.full(n, -inf), "force_hi": np.full(n, inf),
+            "force_lo": np.full(n, -inf), "force_hi": np.full(n, inf), "coulomb_friction": np.zeros(n),
         }
         off = 0
         for i, b in enumerate(self.bodies):
@@ -407,7 +408,7 @@ class ModelDescription:
             a["mass"][i] = b.mass
             a["com"][i] = b.com
             a["inertia"][i] = b.inertia
-            for key in ("damping", "spring", "rest", "pos_lo", "pos_hi", "vel_lo", "vel_hi", "force_lo", "force_hi"):
+            for key in ("damping", "spring", "rest", "pos_lo", "pos_hi", "vel_lo", "vel_hi", "force_lo", "force_hi", "coulomb_friction"):
                 vals = getattr(b, key)
                 if len(vals):
                     if len(vals) != nd:
@@ -455,6 +456,10 @@ class ModelDescription:
             return False
         return True
 
+    def num_friction_dofs(self) -> int:
+        """DOFs with a non-zero Coulomb friction force: each takes one contact slot of the LCP when it moves."""
+        return sum(1 for b in self.bodies for f in b.coulomb_friction if f != 0.0)
+
     def suggest_max_contacts(self) -> int:
         """Contact slots per world for a description that does not say (the loaders' default): the smallest of the library's three budgets that
         the collider pairs of the model cannot exceed in their usual configurations - 8 (the 24-row build, the fast one), 16 (the 48-row
@@ -465,8 +470,9 @@ class ModelDescription:
         several others only as many as can touch it at once are counted (a body has 6 faces; in a pile at most 2 face contacts of 8 + 4 of 4).
         The reference itself keeps every contact (ConstraintSolver.cpp:563-606); a world that exceeds its model's slots is truncated and
         flagged NBL_ST_CONTACT_OVERFLOW."""
+        nfric = self.num_friction_dofs()   # (one slot per friction DOF on top of the contacts: a moving one is a row of the LCP)
         if not self.boxes:
-            return 0
+            return min(128, max(8, (nfric + 7) // 8 * 8)) if nfric else 0
         m = self.merge_welds() if self.has_welds() else self
         skel = m.body_skeletons()
         est = 0
@@ -475,6 +481,7 @@ class ModelDescription:
                 if m.colliders_are_tested(bi, bj, skel):
                     both_move = bi.body >= 0 and bj.body >= 0
                     est += (8 if both_move else 4) if (bi.shape == "box" and bj.shape == "box") else (2 if (bi.shape == "capsule" and bj.shape == "capsule") else 1)
+        est += nfric
         if est <= 8:
             return 8
         if est <= 16:
@@ -524,12 +531,21 @@ class ModelDescription:
         for k in ("T_pj", "T_cj", "axis", "mass", "com", "inertia", "damping", "spring", "rest", "pos_lo", "pos_hi",
                   "vel_lo", "vel_hi", "force_lo", "force_hi", "box_T", "box_size", "box_mu", "box_restitution", "pitch"):
             setattr(d, k, pd(a[k]))
+        nfric = self.num_friction_dofs()
+        if nfric:   # (NULL otherwise: a model without joint friction hands the library exactly what it did before the field existed)
+            d.coulomb_friction = pd(a["coulomb_friction"])
         d.gravity = (C.c_double * 3)(*self.gravity)
         d.dt = self.dt
         d.n_action = len(a["action_map"])
         d.n_boxes = len(self.boxes)
-        # (a joint-limit row takes one of the contact slots of the LCP: a model without colliders that enforces limits still needs them)
+        # (a joint-limit row takes one of the contact slots of the LCP: a model without colliders that enforces limits still needs them; so does
+        #  a joint friction row - one slot per friction DOF, so that a world where every such DOF moves is never truncated.  As with limits,
+        #  slots given for these rows to a model that HAS colliders but max_contacts = 0 also let its colliders make contacts, which then
+        #  compete with the friction rows for the slots: give such a model max_contacts explicitly)
         d.max_contacts = self.max_contacts or (8 if any(b.limit_enforced for b in self.bodies) else 0)
+        if not self.max_contacts and nfric:
+            nlim = sum(_abi.JOINT_NDOF[_abi.JOINT_NAMES[b.joint_type]] for b in self.bodies if b.limit_enforced)
+            d.max_contacts = min(128, max(8, (nfric + nlim + 7) // 8 * 8))
         d.contact_clipping_depth = self.contact_clipping_depth
         d.fallback_cfm = self.fallback_cfm
         d.penetration_correction = 1 if self.penetration_correction else 0
@@ -539,7 +555,7 @@ class ModelDescription:
     def to_json(self) -> dict:
         def body(b: BodySpec):
             d = {k: (np.asarray(v).tolist() if isinstance(v, (np.ndarray, tuple, list)) else v) for k, v in b.__dict__.items()
-                 if k != "axes" and not (k == "skeleton" and v < 0) and not (k == "beta" and tuple(v) == (1.0, 1.0, 1.0)) and not (k in ("limit_enforced", "self_collision", "adjacent_body_check") and not v) and not (k == "pitch" and b.joint_type != "screw")}   # compound joints are already expanded: every stored joint has its single `axis`
+                 if k != "axes" and not (k == "skeleton" and v < 0) and not (k == "beta" and tuple(v) == (1.0, 1.0, 1.0)) and not (k in ("limit_enforced", "self_collision", "adjacent_body_check") and not v) and not (k == "coulomb_friction" and not any(v)) and not (k == "pitch" and b.joint_type != "screw")}   # compound joints are already expanded: every stored joint has its single `axis`
             return d
         return {
             "name": self.name, "gravity": list(self.gravity), "dt": self.dt, "action_map": self._action_map,

@@ -183,14 +183,14 @@ class World:
             self._create_handle()
         except Exception:
             for md, flags in zip(self._descriptions(), snapshot):
-                for b, (le, sc, ab) in zip(md.bodies, flags):
-                    b.limit_enforced, b.self_collision, b.adjacent_body_check = le, sc, ab
+                for b, (le, sc, ab, cf) in zip(md.bodies, flags):
+                    b.limit_enforced, b.self_collision, b.adjacent_body_check, b.coulomb_friction = le, sc, ab, cf
             raise
         if self._wrt_mass.entries:
             self._push_inertia_params()
 
     def _flag_snapshot(self):
-        return [[(b.limit_enforced, b.self_collision, b.adjacent_body_check) for b in md.bodies] for md in self._descriptions()]
+        return [[(b.limit_enforced, b.self_collision, b.adjacent_body_check, b.coulomb_friction) for b in md.bodies] for md in self._descriptions()]
 
     def setPositionLimitEnforced(self, enforced: bool, joints=None):
         """Joint::setPositionLimitEnforced (Joint.cpp:1366) on the named joints / bodies (default: every joint): their position limits
@@ -221,6 +221,35 @@ class World:
 
     def getPositionLimitEnforced(self):
         return {b.joint_name or b.name: bool(b.limit_enforced) for b in self.description.bodies}
+
+    def setCoulombFriction(self, value, joints=None):
+        """Joint::setCoulombFriction (GenericJoint.hpp) on the named joints / bodies (default: every joint with DOFs): `value` is one
+        friction force for every DOF of a joint or a sequence of one per DOF.  A DOF with f != 0 that moves becomes a row of the contact LCP
+        with bounds [-f dt, f dt] (JointCoulombFrictionConstraint.cpp); 0 everywhere by default, like in the reference.  The handle is
+        rebuilt and the LCP warm start dropped, as by setPositionLimitEnforced; a friction model runs the general contact stage.
+        Compound joints (Euler, universal, translational, planar) are stored as their chains of 1-DOF joints, named `<joint>_<i>`: address
+        them per link (a scalar, or a 1-entry sequence); a per-DOF sequence for the whole compound joint is refused."""
+        snapshot, changed = self._flag_snapshot(), False
+        for md in self._descriptions():
+            for b in md.bodies:
+                nd = _abi.JOINT_NDOF[_abi.JOINT_NAMES[b.joint_type]]
+                if nd == 0 or not (joints is None or b.joint_name in joints or b.name in joints):
+                    continue
+                vals = tuple(float(v) for v in value) if np.ndim(value) else (float(value),) * nd
+                if len(vals) != nd:
+                    raise ValueError(f"{b.joint_name or b.name}: {len(vals)} friction values for a {nd}-DOF joint")
+                new = vals if any(vals) else ()
+                if tuple(b.coulomb_friction) != new:
+                    b.coulomb_friction = new
+                    changed = True
+        if changed:
+            self._reupload_or_roll_back(snapshot)
+
+    def getCoulombFriction(self):
+        """Per stored joint: the Coulomb friction force of each of its DOFs (Joint::getCoulombFriction); a compound joint appears as its
+        1-DOF links `<joint>_<i>`, one entry each."""
+        return {b.joint_name or b.name: tuple(b.coulomb_friction) or (0.0,) * _abi.JOINT_NDOF[_abi.JOINT_NAMES[b.joint_type]]
+                for b in self.description.bodies}
 
     def removeDofFromActionSpace(self, index: int):
         self.setActionSpace([a for a in self.getActionSpace() if a != index])
