@@ -229,7 +229,10 @@ const char* nbl_last_error(void);
  *            + nbl_kin_map_create, nbl_kin_map_destroy, nbl_kin_map_dim, nbl_kinematics_forward, nbl_kinematics_backward (world-space
  *            kinematics of body frames, below: added without a new minor number - a caller that needs them looks the symbols up);
  *            + coulomb_friction, NBL_ST_JOINT_FRICTION (appended without a new minor number, like the kinematics entries: a library
- *            built before the field ignores it, so a caller that depends on it checks for NBL_ST_JOINT_FRICTION in the status). */
+ *            built before the field ignores it, so a caller that depends on it checks for NBL_ST_JOINT_FRICTION in the status).
+ *            + nbl_dynamics_workspace_bytes, nbl_inverse_dynamics_forward, nbl_inverse_dynamics_backward, nbl_mass_matrix (joint-space
+ *            dynamics quantities, below: appended without a new minor number, like the kinematics entries - the model description did
+ *            not change; a caller that needs them looks the symbols up). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -483,6 +486,33 @@ int32_t nbl_kinematics_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, co
  * nbl_kinematics_forward; no atomics: bit-reproducible. */
 int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* grad_pos,
                                 const double* grad_vel, double* grad_state, int32_t accumulate, void* stream);
+/* ---- joint-space dynamics quantities (csrc/dynamics.hip) -------------------------------------------------------------------------------
+ * Inverse dynamics  tau = M(q) a + C(q, v)  by the recursive Newton-Euler algorithm (Skeleton::getInverseDynamics, Skeleton.cpp:9658-9666),
+ * the Coriolis-and-gravity vector C(q, v) (a = 0; World::getCoriolisAndGravityForces, World.cpp:1965-1986) and the mass matrix M(q)
+ * (World::getMassMatrix, World.cpp:1943-1963; composite-rigid-body algorithm) of B worlds, one world per lane, with the exact
+ * vector-Jacobian product of the first.  They read the handle's CURRENT body inertias (nbl_set_body_inertia(s), nbl_set_inertia_params).
+ * state [2n][B] = [q; v], accel / tau / grad_* [n][B], M [n * n][B] (row-major n x n per world), device pointers, SoA like the step's.
+ * B may be (T + 1) x worlds: a whole rollout in one launch.  workspace: device scratch of nbl_dynamics_workspace_bytes(m, B) bytes (one
+ * size serves the three calls); calls that share a workspace must be ordered on one stream.  Stream-ordered, no synchronisation, no
+ * atomics: bit-reproducible.  Not covered: the inverse mass matrix, external forces, Skeleton::getInverseDynamicsFromPredictions. */
+#define NBL_ID_NO_VELOCITY 1  /* take v as 0 */
+#define NBL_ID_NO_GRAVITY 2   /* leave gravity out */
+#define NBL_ID_JOINT_FORCES 4 /* + damping v + spring (q - rest + dt v) per DOF: the terms nbl_step_forward puts on the right-hand side, so
+                                 that tau fed to the step as the joint torques reproduces a */
+size_t nbl_dynamics_workspace_bytes(const nbl_model* m, int64_t B);
+/* tau = M(q) a + C(q, v).  accel NULL: a = 0 (tau = C).  Errors: NBL_E_BADARG (null handle / state / tau / workspace, B < 0, unknown
+ * flag bits), NBL_E_WORKSPACE (workspace_bytes < nbl_dynamics_workspace_bytes(m, B)).  B = 0 is a no-op. */
+int32_t nbl_inverse_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags, double* tau,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+/* The reverse pass: grad_state [2n][B] = (accumulate: +=) (d tau / d [q; v])^T grad_tau, grad_accel [n][B] = (+=) M^T grad_tau; either may
+ * be NULL.  Both blocks of grad_state are exact (with NBL_ID_NO_VELOCITY the velocity block receives nothing); free and ball coordinates
+ * are differentiated analytically through expMapJac (FreeJoint.cpp:790-823, BallJoint.cpp:282-289). */
+int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
+                                      const double* grad_tau, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+/* M(q): symmetric, both triangles written (M[i][j] and M[j][i] are the same bits).  Only the position block of state is read. */
+int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream);
+
 /* enabled = 0: off (and reset); 1: HIP events around every kernel launch; N > 1: around the launches of every N-th forward /
  * backward call only (sampling keeps the perturbation of a timed region below 1 %). */
 int32_t nbl_set_timing(nbl_model* m, int32_t enabled);

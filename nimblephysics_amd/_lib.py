@@ -122,6 +122,14 @@ def lib():
     L.nbl_kinematics_forward.restype = C.c_int32
     L.nbl_kinematics_backward.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int32, vp]
     L.nbl_kinematics_backward.restype = C.c_int32
+    L.nbl_dynamics_workspace_bytes.argtypes = [vp, C.c_int64]
+    L.nbl_dynamics_workspace_bytes.restype = C.c_size_t
+    L.nbl_inverse_dynamics_forward.argtypes = [vp, C.c_int64, vp, vp, C.c_int32, vp, vp, C.c_size_t, vp]
+    L.nbl_inverse_dynamics_forward.restype = C.c_int32
+    L.nbl_inverse_dynamics_backward.argtypes = [vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_inverse_dynamics_backward.restype = C.c_int32
+    L.nbl_mass_matrix.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_mass_matrix.restype = C.c_int32
     _lib = L
     return L
 
@@ -135,6 +143,7 @@ EXPORTED_SYMBOLS = [
     "nbl_get_timing", "nbl_kernel_count", "nbl_kernel_name", "nbl_kernel_timing", "nbl_selftest_lcp_dantzig", "nbl_selftest_lcp_dantzig_timed", "nbl_selftest_lcp_cascade", "nbl_selftest_pinv",
     "nbl_model_max_contacts", "nbl_selftest_pinv_rows",
     "nbl_kin_map_create", "nbl_kin_map_destroy", "nbl_kin_map_dim", "nbl_kinematics_forward", "nbl_kinematics_backward",
+    "nbl_dynamics_workspace_bytes", "nbl_inverse_dynamics_forward", "nbl_inverse_dynamics_backward", "nbl_mass_matrix",
 ]
 
 

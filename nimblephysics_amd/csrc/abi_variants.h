@@ -75,6 +75,10 @@
 #define nbl_kin_map_dim NBL_V(nbl_kin_map_dim)
 #define nbl_kinematics_forward NBL_V(nbl_kinematics_forward)
 #define nbl_kinematics_backward NBL_V(nbl_kinematics_backward)
+#define nbl_dynamics_workspace_bytes NBL_V(nbl_dynamics_workspace_bytes)
+#define nbl_inverse_dynamics_forward NBL_V(nbl_inverse_dynamics_forward)
+#define nbl_inverse_dynamics_backward NBL_V(nbl_inverse_dynamics_backward)
+#define nbl_mass_matrix NBL_V(nbl_mass_matrix)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

@@ -1,0 +1,43 @@
+// dynamics.hip — joint-space dynamics quantities for B worlds (nbl_inverse_dynamics_forward / _backward, nbl_mass_matrix): the device side
+// of Skeleton::getInverseDynamics, World::getCoriolisAndGravityForces and World::getMassMatrix and of their vector-Jacobian products
+// (nimblephysics_amd/dynamics.py).  The math is in dynamics_dev.hpp.
+//
+// ONE WORLD PER LANE, like k_step_forward's Ctx path and the kinematics kernels: the body constants are wave-uniform (scalar loads), and
+// the per-body T / V / A / F and their adjoints, which must survive between the two tree sweeps, live in the caller's workspace laid out
+// [body][slot][B], so every access of a wavefront is one coalesced line and a lane holds one body's quantities in registers at a time.
+// B may be (T + 1) x worlds, or n x worlds (the mass matrix's backward pass): 64-bit world indices throughout.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dynamics_dev.hpp"
+
+namespace NBL_NS {
+
+constexpr int DYN_BLOCK = 64;
+
+__global__ __launch_bounds__(DYN_BLOCK) void k_inverse_dynamics(const DevBody* __restrict__ bodies, const DevDof* __restrict__ dofs, DevModel mdl,
+                                                                int flags, int64_t B, const double* __restrict__ state,
+                                                                const double* __restrict__ accel, double* __restrict__ tau, double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  idForwardWorld(bodies, dofs, mdl.nb, mdl.n, mdl.gravity, mdl.dt, flags, B, b, state, accel, tau, ws);
+}
+
+__global__ __launch_bounds__(DYN_BLOCK) void k_inverse_dynamics_vjp(const DevBody* __restrict__ bodies, const DevDof* __restrict__ dofs, DevModel mdl,
+                                                                    int flags, int64_t B, const double* __restrict__ state,
+                                                                    const double* __restrict__ accel, const double* __restrict__ gtau,
+                                                                    double* __restrict__ gstate, double* __restrict__ gaccel, int accumulate,
+                                                                    double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  idVjpWorld(bodies, dofs, mdl.nb, mdl.n, mdl.gravity, mdl.dt, flags, B, b, state, accel, gtau, gstate, gaccel, accumulate, ws);
+}
+
+__global__ __launch_bounds__(DYN_BLOCK) void k_mass_matrix(const DevBody* __restrict__ bodies, DevModel mdl, int64_t B,
+                                                           const double* __restrict__ state, double* __restrict__ M, double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  massMatrixWorld(bodies, mdl.nb, mdl.n, B, b, state, M, ws);
+}
+
+}  // namespace NBL_NS

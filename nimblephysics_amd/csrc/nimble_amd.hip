@@ -26,6 +26,7 @@
 #include "coop_tree.hip"
 #include "inertia_backward.hip"
 #include "kinematics.hip"
+#include "dynamics.hip"
 
 using namespace NBL_NS;
 
@@ -1724,6 +1725,68 @@ int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, c
   hipLaunchKernelGGL(k_kinematics_vjp, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
                      (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, grad_pos,
                      grad_vel, grad_state, accumulate ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// ---- joint-space dynamics quantities (inverse dynamics, Coriolis and gravity, mass matrix; csrc/dynamics.hip) --------------------------
+size_t nbl_dynamics_workspace_bytes(const nbl_model* m, int64_t B) {
+  if (!m || B <= 0) return 0;
+  return sizeof(double) * (size_t)m->nb * DYN_SLOTS * (size_t)B;
+}
+
+static int32_t dynCheck(const nbl_model* m, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (B == 0) return NBL_OK;
+  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
+  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  const size_t need = nbl_dynamics_workspace_bytes(m, B);
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "dynamics workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_dynamics_workspace_bytes() = " + std::to_string(need));
+  return NBL_OK;
+}
+static int32_t dynFlags(int32_t flags) {
+  if (flags & ~DYN_FLAG_MASK) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~DYN_FLAG_MASK) + " (NBL_ID_*)");
+  return NBL_OK;
+}
+
+int32_t nbl_inverse_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags, double* tau,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  int32_t rc = dynCheck(m, B, state, tau, workspace, workspace_bytes);
+  if (rc == NBL_OK) rc = dynFlags(flags);
+  if (rc != NBL_OK || B == 0) return rc;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_inverse_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, tau, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
+                                      const double* grad_tau, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  int32_t rc = dynCheck(m, B, state, grad_tau, workspace, workspace_bytes);
+  if (rc == NBL_OK) rc = dynFlags(flags);
+  if (rc != NBL_OK || B == 0) return rc;
+  if (!grad_state && !grad_accel) return NBL_OK;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_inverse_dynamics_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, grad_tau, grad_state, grad_accel,
+                     accumulate ? 1 : 0, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = dynCheck(m, B, state, M, workspace, workspace_bytes);
+  if (rc != NBL_OK || B == 0) return rc;
+  DeviceGuard guard(m->device);
+  HIP_TRY(hipMemsetAsync(M, 0, sizeof(double) * (size_t)m->n * m->n * (size_t)B, (hipStream_t)stream));   // unrelated DOFs: the kernel writes the rest
+  hipLaunchKernelGGL(k_mass_matrix, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, m->mdl, B, state, M, (double*)workspace);
   HIP_TRY(hipGetLastError());
   return NBL_OK;
 }

@@ -68,7 +68,12 @@
   void nbl_kin_map_destroy##S(void*);                                                                                                      \
   int32_t nbl_kin_map_dim##S(const void*);                                                                                                 \
   int32_t nbl_kinematics_forward##S(void*, const void*, int64_t, const double*, double*, double*, void*);                                  \
-  int32_t nbl_kinematics_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, double*, int32_t, void*);
+  int32_t nbl_kinematics_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, double*, int32_t, void*); \
+  size_t nbl_dynamics_workspace_bytes##S(const void*, int64_t);                                                                            \
+  int32_t nbl_inverse_dynamics_forward##S(void*, int64_t, const double*, const double*, int32_t, double*, void*, size_t, void*);           \
+  int32_t nbl_inverse_dynamics_backward##S(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, \
+                                           void*, size_t, void*);                                                                          \
+  int32_t nbl_mass_matrix##S(void*, int64_t, const double*, double*, void*, size_t, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -124,6 +129,10 @@ struct Variant {
   int32_t (*kin_map_dim)(const void*);
   int32_t (*kinematics_forward)(void*, const void*, int64_t, const double*, double*, double*, void*);
   int32_t (*kinematics_backward)(void*, const void*, int64_t, const double*, const double*, const double*, double*, int32_t, void*);
+  size_t (*dynamics_workspace_bytes)(const void*, int64_t);
+  int32_t (*inverse_dynamics_forward)(void*, int64_t, const double*, const double*, int32_t, double*, void*, size_t, void*);
+  int32_t (*inverse_dynamics_backward)(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, void*, size_t, void*);
+  int32_t (*mass_matrix)(void*, int64_t, const double*, double*, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -134,7 +143,8 @@ struct Variant {
    nbl_selftest_lcp_dantzig_timed##S, nbl_selftest_pinv_rows##S, nbl_set_launch_lanes##S, nbl_set_slices##S, nbl_slices_for##S,               \
    nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
    nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_kin_map_create##S, nbl_kin_map_destroy##S, nbl_kin_map_dim##S,          \
-   nbl_kinematics_forward##S, nbl_kinematics_backward##S}
+   nbl_kinematics_forward##S, nbl_kinematics_backward##S, nbl_dynamics_workspace_bytes##S, nbl_inverse_dynamics_forward##S,                 \
+   nbl_inverse_dynamics_backward##S, nbl_mass_matrix##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -349,6 +359,21 @@ int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, c
   if (!k) return ownError(NBL_E_BADARG, "null kinematics map");
   if (m && k->v != m->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model");
   return NBL_FWD(m, kinematics_backward, k->impl, B, state, grad_pos, grad_vel, grad_state, accumulate, stream);
+}
+
+size_t nbl_dynamics_workspace_bytes(const nbl_model* m, int64_t B) { return m ? m->v->dynamics_workspace_bytes(m->impl, B) : 0; }
+int32_t nbl_inverse_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags, double* tau,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return NBL_FWD(m, inverse_dynamics_forward, B, state, accel, flags, tau, workspace, workspace_bytes, stream);
+}
+int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags, const double* grad_tau,
+                                      double* grad_state, double* grad_accel, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return NBL_FWD(m, inverse_dynamics_backward, B, state, accel, flags, grad_tau, grad_state, grad_accel, accumulate, workspace, workspace_bytes,
+                 stream);
+}
+int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream) {
+  return NBL_FWD(m, mass_matrix, B, state, M, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,218 @@
+"""Joint-space dynamics quantities for batches of states: `inverse_dynamics`, `coriolis_and_gravity`, `mass_matrix`
+(Skeleton::getInverseDynamics, dart/dynamics/Skeleton.cpp:9658-9666; World::getCoriolisAndGravityForces and World::getMassMatrix,
+dart/simulation/World.cpp:1943-1986), with exact gradients.
+
+    tau = inverse_dynamics(world, state, accel)        [..., 2n], [..., n] -> [..., n]      tau = M(q) a + C(q, v)
+    C   = coriolis_and_gravity(world, state)           [..., 2n] -> [..., n]                 inverse_dynamics with a = 0
+    M   = mass_matrix(world, state)                    [..., 2n] -> [..., n, n]
+
+Each is one launch of csrc/dynamics.hip over all the leading dimensions (`[2n]` is one world, `[B, 2n]` a batch, `[B, T+1, 2n]` - what
+`rollout()` returns - a whole trajectory), differentiable with respect to `state` and `accel`: recursive Newton-Euler with its exact
+reverse pass (positions AND velocities; free and ball coordinates analytically through expMapJac), the composite-rigid-body algorithm for
+M, whose backward pass is one reverse launch over n x B worlds (world (j, b): a = e_j, cotangent G[b, :, j], no velocity, no gravity;
+above MASS_BACKWARD_WORLDS = 262144 launched worlds it is cut into launches of whole columns, which bounds the workspace).
+The kernels read the World's current body inertias (World.setMasses).  With `joint_forces=True`, tau also carries
+damping v + spring (q - rest + dt v) per coordinate - the terms the step puts on the right-hand side - so that tau applied as the joint
+torques of `timestep()` reproduces `accel`.
+
+Rules shared with mapping.py: CPU float64 tensors come back as CPU tensors, device tensors stay on the device; the World's state is left
+untouched; a World in deferred-join mode is joined first.  On a world with immobile skeletons a `state` (and `accel`) in the reference's
+layout is restricted to the mobile coordinates as map_to_pos does; the outputs are over the MOBILE coordinates and the gradients of the
+frozen entries are zero.  The reference's own mass matrix has blocks for the immobile skeletons (their bodies keep their masses there),
+which this model - it welded them to the world - cannot give.
+
+Out of scope: the inverse mass matrix (World::getInvMassMatrix), external forces on bodies, and
+Skeleton::getInverseDynamicsFromPredictions.
+"""
+from __future__ import annotations
+
+
+import torch
+
+from ._lib import check
+from .mapping import _join_if_deferred, _ptr
+
+ID_NO_VELOCITY, ID_NO_GRAVITY, ID_JOINT_FORCES = 1, 2, 4      # NBL_ID_* of include/nimble_amd.h
+# mass_matrix's backward pass launches the reverse kernel over (columns x B) worlds, and the workspace is 48 doubles per body and launched
+# world (Atlas-33, 34 bodies: 13 kB per world - 1.8 GB for all 33 columns of 4096 worlds).  Up to this many worlds go into ONE launch
+# (3.4 GB of workspace on Atlas-33); a larger batch - 32768 worlds, or a [B, T+1] rollout - is cut into launches of whole columns.
+MASS_BACKWARD_WORLDS = 1 << 18
+
+
+def _workspace(world, B: int):
+    """The dynamics scratch of the World: one buffer, grown to the largest B seen (like World._workspace)."""
+    need = world._L.nbl_dynamics_workspace_bytes(world._h, B)
+    ws = getattr(world, "_dyn_ws", None)
+    if ws is None or ws.numel() < need or ws.device != world.device:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=world.device)
+        world._dyn_ws = ws
+    return ws
+
+
+# ---- raw SoA calls: state [2n][B], accel / tau [n][B], M [n * n][B] on the World's device ----
+def inverse_dynamics_soa(world, s_soa: torch.Tensor, a_soa, flags: int = 0) -> torch.Tensor:
+    B = s_soa.shape[1]
+    tau = torch.empty((world.n, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        ws = _workspace(world, B)
+        check(world._L.nbl_inverse_dynamics_forward(world._h, B, _ptr(s_soa), _ptr(a_soa), flags, _ptr(tau), _ptr(ws), ws.numel(), world._stream()),
+              "nbl_inverse_dynamics_forward")
+    return tau
+
+
+def inverse_dynamics_vjp_soa(world, s_soa: torch.Tensor, a_soa, g_soa: torch.Tensor, flags: int = 0, want_accel: bool = True):
+    B = s_soa.shape[1]
+    gs = torch.empty((2 * world.n, B), dtype=torch.float64, device=world.device)
+    ga = torch.empty((world.n, B), dtype=torch.float64, device=world.device) if want_accel else None
+    if B > 0:
+        ws = _workspace(world, B)
+        check(world._L.nbl_inverse_dynamics_backward(world._h, B, _ptr(s_soa), _ptr(a_soa), flags, _ptr(g_soa), _ptr(gs), _ptr(ga), 0, _ptr(ws),
+                                                     ws.numel(), world._stream()), "nbl_inverse_dynamics_backward")
+    return gs, ga
+
+
+def mass_matrix_soa(world, s_soa: torch.Tensor) -> torch.Tensor:
+    B = s_soa.shape[1]
+    M = torch.empty((world.n * world.n, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        ws = _workspace(world, B)
+        check(world._L.nbl_mass_matrix(world._h, B, _ptr(s_soa), _ptr(M), _ptr(ws), ws.numel(), world._stream()), "nbl_mass_matrix")
+    return M
+
+
+def _restrict(world, x: torch.Tensor, what: str, block: str):
+    """(the tensor over the device's coordinates, whether it came in the reference's layout, its width)"""
+    lay = world.ref_layout
+    per = 2 if block == "state" else 1
+    width = x.shape[-1] if x.dim() > 0 else -1
+    ref = lay is not None and width == per * lay.n_ref
+    if ref:
+        x = lay.restrict_state(x, what, check_frozen=False) if block == "state" else x.index_select(-1, lay._idx(x.device, "mobile"))
+    if x.dim() == 0 or x.shape[-1] != per * world.n:
+        want = f"{per * world.n}" + (f" (or {per * lay.n_ref} in the reference's layout)" if lay is not None else "")
+        raise ValueError(f"{what}: {block} has {width} entries per world; expected {want}")
+    return x, ref, width
+
+
+def _expand(world, d: torch.Tensor, lead, width: int, block: str) -> torch.Tensor:
+    lay = world.ref_layout
+    return torch.zeros(lead + (width,), dtype=torch.float64, device=world.device).index_copy(-1, lay._idx(world.device, "state" if block == "state" else "mobile"), d)
+
+
+def _give(world, t: torch.Tensor, like_device):
+    return world._to_host(t) if like_device.type == "cpu" else t.to(like_device)
+
+
+class InverseDynamicsLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, world, state, accel, flags):
+        _join_if_deferred(world)                                  # before anything reads `state`: it may come out of the slices
+        n = world.n
+        x, ctx.ref_s, ctx.width_s = _restrict(world, state.detach(), "inverse_dynamics", "state")
+        lead = tuple(x.shape[:-1])
+        s_soa = world.to_soa(world._prep(x.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+        a_soa = None
+        if accel is not None:
+            a, ctx.ref_a, ctx.width_a = _restrict(world, accel.detach(), "inverse_dynamics", "accel")
+            if tuple(a.shape[:-1]) != lead:
+                raise ValueError(f"inverse_dynamics: accel has leading shape {tuple(a.shape[:-1])}, state {lead}")
+            a_soa = world.to_soa(world._prep(a.reshape(-1, n), n, "dyn_accel"))
+            ctx.accel_device = accel.device
+        tau = inverse_dynamics_soa(world, s_soa, a_soa, flags)
+        out = world.from_soa(tau).reshape(lead + (n,))
+        ctx.world, ctx.s_soa, ctx.a_soa, ctx.flags, ctx.lead, ctx.state_device = world, s_soa, a_soa, flags, lead, state.device
+        return _give(world, out, state.device)
+
+    @staticmethod
+    def backward(ctx, grad_tau):
+        world, n, lead = ctx.world, ctx.world.n, ctx.lead
+        g = grad_tau.detach().to(device=world.device, dtype=torch.float64).reshape(-1, n)
+        want_a = ctx.a_soa is not None and ctx.needs_input_grad[2]
+        gs, ga = inverse_dynamics_vjp_soa(world, ctx.s_soa, ctx.a_soa, world.to_soa(g), ctx.flags, want_a)
+        ds = world.from_soa(gs).reshape(lead + (2 * n,))
+        if ctx.ref_s:                                             # zero for the frozen coordinates
+            ds = _expand(world, ds, lead, ctx.width_s, "state")
+        da = None
+        if want_a:
+            da = world.from_soa(ga).reshape(lead + (n,))
+            if ctx.ref_a:
+                da = _expand(world, da, lead, ctx.width_a, "accel")
+        ds = _give(world, ds, ctx.state_device)
+        if want_a:
+            da = _give(world, da, ctx.accel_device)
+        return None, ds, da, None
+
+
+class MassMatrixLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, world, state):
+        _join_if_deferred(world)
+        n = world.n
+        x, ctx.ref_s, ctx.width_s = _restrict(world, state.detach(), "mass_matrix", "state")
+        lead = tuple(x.shape[:-1])
+        s_soa = world.to_soa(world._prep(x.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+        M = mass_matrix_soa(world, s_soa)
+        out = world.from_soa(M).reshape(lead + (n, n))
+        ctx.world, ctx.s_soa, ctx.lead, ctx.state_device = world, s_soa, lead, state.device
+        return _give(world, out, state.device)
+
+    @staticmethod
+    def backward(ctx, grad_M):
+        """A reverse launch over n x B worlds (cut into whole columns above MASS_BACKWARD_WORLDS): world j * B + b has a = e_j and the cotangent G[b, :, j] (tau = M e_j is column j)."""
+        world, n, lead = ctx.world, ctx.world.n, ctx.lead
+        G = grad_M.detach().to(device=world.device, dtype=torch.float64).reshape(-1, n, n)
+        B = G.shape[0]
+        # columns j0 .. j1 per launch: all n at once while n x B stays within MASS_BACKWARD_WORLDS (the workspace is per launched world)
+        per = max(1, min(n, MASS_BACKWARD_WORLDS // max(B, 1)))
+        eye_n = torch.eye(n, dtype=torch.float64, device=world.device)
+        Gt = G.permute(1, 2, 0)                                   # [i, j, b]
+        gq = torch.zeros((n, B), dtype=torch.float64, device=world.device)
+        for j0 in range(0, n, per):
+            j1 = min(n, j0 + per)
+            rep = ctx.s_soa.repeat(1, j1 - j0)
+            eye = eye_n[:, j0:j1].repeat_interleave(B, dim=1)
+            gt = Gt[:, j0:j1].reshape(n, (j1 - j0) * B).contiguous()
+            gs, _ = inverse_dynamics_vjp_soa(world, rep, eye, gt, ID_NO_VELOCITY | ID_NO_GRAVITY, want_accel=False)
+            part = gs[:n].reshape(n, j1 - j0, B)
+            for j in range(j1 - j0):                              # summed column by column: the bits do not depend on the chunking
+                gq += part[:, j]
+        ds = world.from_soa(torch.cat([gq, torch.zeros_like(gq)], 0)).reshape(lead + (2 * n,))
+        if ctx.ref_s:
+            ds = _expand(world, ds, lead, ctx.width_s, "state")
+        return None, _give(world, ds, ctx.state_device)
+
+
+def inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, joint_forces: bool = False) -> torch.Tensor:
+    """tau = M(q) a + C(q, v) of `state` = [q; v] ([..., 2n]) and `accel` ([..., n]) -> [..., n]; differentiable in both (exactly).
+    joint_forces: + damping v + spring (q - rest + dt v), so that tau applied in timestep() reproduces accel."""
+    return InverseDynamicsLayer.apply(world, state, accel, ID_JOINT_FORCES if joint_forces else 0)
+
+
+def coriolis_and_gravity(world, state: torch.Tensor) -> torch.Tensor:
+    """C(q, v): Coriolis, centrifugal and gravity forces of `state` ([..., 2n] -> [..., n]) = inverse_dynamics with a = 0."""
+    return InverseDynamicsLayer.apply(world, state, None, 0)
+
+
+def mass_matrix(world, state: torch.Tensor) -> torch.Tensor:
+    """M(q) of `state` ([..., 2n] -> [..., n, n]; only the positions are read), exactly symmetric; differentiable in the positions."""
+    return MassMatrixLayer.apply(world, state)
+
+
+def _current(world):
+    from ._lib import NimbleAmdError
+    if getattr(world, "_state", None) is None:
+        raise NimbleAmdError("call world.setState() first")
+    _join_if_deferred(world)
+    return world._state
+
+
+def world_mass_matrix(world) -> torch.Tensor:
+    s = _current(world)
+    M = world.from_soa(mass_matrix_soa(world, s)).reshape(s.shape[1], world.n, world.n)
+    return M[0] if getattr(world, "_one_d", False) else M
+
+
+def world_coriolis_and_gravity(world) -> torch.Tensor:
+    s = _current(world)
+    c = world.from_soa(inverse_dynamics_soa(world, s, None, 0))
+    return c[0] if getattr(world, "_one_d", False) else c

@@ -359,6 +359,18 @@ class World:
             out = full.index_copy(1, cols, out)
         return out
 
+    # ---- joint-space dynamics of the current state (dynamics.py; World.cpp:1943-1986) --------------
+    def getMassMatrix(self) -> torch.Tensor:
+        """World::getMassMatrix on the current state: [B, n, n] on the World's device ([n, n] when the state was set as one 1-D vector),
+        over the device's (mobile) coordinates.  The state is left untouched."""
+        from .dynamics import world_mass_matrix
+        return world_mass_matrix(self)
+
+    def getCoriolisAndGravityForces(self) -> torch.Tensor:
+        """World::getCoriolisAndGravityForces on the current state: [B, n] ([n] for a 1-D state); see getMassMatrix."""
+        from .dynamics import world_coriolis_and_gravity
+        return world_coriolis_and_gravity(self)
+
     def reset_lcp_cache(self):
         self.lcp_cache = None
 

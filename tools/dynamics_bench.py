@@ -1,0 +1,83 @@
+"""Developer tool: time the joint-space dynamics entry points next to the contact-free step, in one process on the same states.
+    python tools/dynamics_bench.py [--reps 30] [--out FILE.json] [--models atlas20,atlas33] [--batches 4096,32768]
+Atlas-20 and Atlas-33 at B = 4096 and 32768: nbl_inverse_dynamics_forward, nbl_inverse_dynamics_backward, nbl_mass_matrix, the n x B
+reverse launch of mass_matrix's backward pass, and nbl_step_forward (no colliders, record kept).  HIP events around every call on
+preallocated buffers, 5 warm-up calls, the median of --reps; one JSON line per configuration."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+import nimblephysics_amd as na
+from nimblephysics_amd.dynamics import ID_NO_GRAVITY, ID_NO_VELOCITY, _workspace
+
+
+def median_ms(fn, reps, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--models", default="atlas20,atlas33")
+    ap.add_argument("--batches", default="4096,32768")     # (one model and one batch with few --reps: what a rocprofv3 --kernel-trace --stats run wants)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    rows = []
+    for variant in args.models.split(","):
+        md = na.atlas(variant)
+        n = md.num_dofs
+        for B in (int(x) for x in args.batches.split(",")):
+            w = na.World(md, device=dev)
+            L, h = w._L, w._h
+            rng = np.random.default_rng(0)
+            s = torch.tensor(np.concatenate([rng.normal(0, 0.5, (n, B)), rng.normal(0, 1.0, (n, B))]), device=dev)
+            a = torch.tensor(rng.normal(0, 2.0, (n, B)), device=dev)
+            g = torch.tensor(rng.normal(0, 1.0, (n, B)), device=dev)
+            tau, gs, ga = torch.empty_like(a), torch.empty_like(s), torch.empty_like(a)
+            M = torch.empty((n * n, B), dtype=torch.float64, device=dev)
+            ws = _workspace(w, n * B)
+            st = w._stream()
+            r = {"model": variant, "n": n, "B": B, "reps": args.reps}
+            r["inverse_dynamics_forward_ms"] = median_ms(lambda: L.nbl_inverse_dynamics_forward(h, B, p(s), p(a), 0, p(tau), p(ws), ws.numel(), st), args.reps)
+            r["inverse_dynamics_backward_ms"] = median_ms(lambda: L.nbl_inverse_dynamics_backward(h, B, p(s), p(a), 0, p(g), p(gs), p(ga), 0, p(ws), ws.numel(), st), args.reps)
+            r["mass_matrix_ms"] = median_ms(lambda: L.nbl_mass_matrix(h, B, p(s), p(M), p(ws), ws.numel(), st), args.reps)
+            rep, eye, gt = s.repeat(1, n), torch.eye(n, dtype=torch.float64, device=dev).repeat_interleave(B, dim=1), torch.randn((n, n * B), dtype=torch.float64, device=dev)
+            gbig = torch.empty((2 * n, n * B), dtype=torch.float64, device=dev)
+            r["mass_matrix_backward_launch_ms"] = median_ms(lambda: L.nbl_inverse_dynamics_backward(h, n * B, p(rep), p(eye), ID_NO_VELOCITY | ID_NO_GRAVITY, p(gt), p(gbig), None, 0, p(ws), ws.numel(), st), args.reps)
+            del rep, eye, gt, gbig
+            u = torch.zeros((w.k, B), dtype=torch.float64, device=dev)
+            nxt, saved = torch.empty_like(s), torch.empty(w.saved_bytes(B), dtype=torch.uint8, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            r["step_forward_ms"] = median_ms(lambda: w.step_into(s, u, nxt, saved, status), args.reps)
+            r["id_forward_over_step"] = r["inverse_dynamics_forward_ms"] / r["step_forward_ms"]
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+            del w, ws
+            torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
