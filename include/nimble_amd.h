@@ -232,7 +232,9 @@ const char* nbl_last_error(void);
  *            built before the field ignores it, so a caller that depends on it checks for NBL_ST_JOINT_FRICTION in the status).
  *            + nbl_dynamics_workspace_bytes, nbl_inverse_dynamics_forward, nbl_inverse_dynamics_backward, nbl_mass_matrix (joint-space
  *            dynamics quantities, below: appended without a new minor number, like the kinematics entries - the model description did
- *            not change; a caller that needs them looks the symbols up). */
+ *            not change; a caller that needs them looks the symbols up).
+ *            + nbl_ik_config, nbl_ik_default_config, nbl_ik_workspace_bytes, nbl_ik_solve (batched inverse kinematics, below: appended
+ *            without a new minor number, like the kinematics and dynamics entries). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -512,6 +514,44 @@ int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* sta
                                       size_t workspace_bytes, void* stream);
 /* M(q): symmetric, both triangles written (M[i][j] and M[j][i] are the same bits).  Only the position block of state is read. */
 int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- batched inverse kinematics (csrc/ik.hip) --------------------------------------------------------------------------------------------
+ * IKMapping::setPositions (dart/neural/IKMapping.cpp:86-119) for B independent worlds: find joint positions whose mapped rows (the rows
+ * of nbl_kinematics_forward) meet `target`.  The kernel restates math::solveIK with ONE restart and math::refineIK
+ * (dart/math/IKSolver.cpp:195-493) operation by operation, one world per lane: refineIK for 20 steps from q_init (unclamped unless
+ * start_clamped), then refineIK for max_step_count steps from that result; refineIK's ladder on errorChange (the 1e-21 stop, halving of
+ * lr with the switch to transpose mode below 1e-4, the line search back to the last iterate, the vanishing-lr stop below 1e-10, the
+ * convergence branch that goes to transpose mode with lr <= 5e-5, then turns clamping on, then stops, lr *= 1.1 otherwise), clamping
+ * forced on the last steps (i > max_step_count - 5), the update pos <- clamp?(pos - lr delta).  J is IKMapping::getPosJacobian, the exact
+ * derivative nbl_kinematics_backward applies, built densely per world.  Clamping is Skeleton::clampPositionsToLimits
+ * (dart/dynamics/Skeleton.cpp:3642-3740) on the model's pos_lo / pos_hi: the clamp per coordinate (the routine's 2 pi candidates for
+ * revolute coordinates never change its result: csrc/ik_dev.hpp), then logMap(expMapRot(.)) of the rotation coordinates of free and ball
+ * joints.  Random restarts are not offered (setPositions' own restart callback is assert(false)).
+ * Two departures from the reference:
+ *   1. the damped-least-squares step.  The reference factors J J^T + lambda I when n < P and J^T J + lambda I otherwise - the LARGER of
+ *      the two, up to 384 x 384.  The two give the same step in exact arithmetic, J^T (J J^T + lambda I)^-1 = (J^T J + lambda I)^-1 J^T;
+ *      the kernel factors the SMALLER one (min(P, n) <= 64 on a side) by an in-place Cholesky and two triangular solves.
+ *      least_squares_damping = 0 (the reference's complete orthogonal decomposition) is NBL_E_UNSUPPORTED;
+ *   2. `loss` is |rows(q_out) - target|^2 AT the returned positions, from one evaluation after the loop (refineIK's lastError belongs to
+ *      an earlier iterate, and solveIK returns the 20-step phase's loss).
+ * target [P][B], q_init / q_out [n][B], loss [B], steps [B] (the number of eval calls over both phases): DEVICE pointers, SoA like
+ * the step's.  q_init NULL: zeros (setPositions).  config NULL: setPositions' configuration (the defaults with max_step_count = 500).
+ * workspace: nbl_ik_workspace_bytes(m, k, B) bytes of device scratch (3 n + P + min(P, n) + P n + min(P, n)^2 doubles per world).
+ * Errors: NBL_E_BADARG (null handle / map / target / q_out / workspace, B < 0, max_step_count < 1 or > 100000, negative damping or threshold),
+ * NBL_E_WORKSPACE (workspace too small), NBL_E_UNSUPPORTED (damping = 0); nothing is launched then.  B = 0 is a no-op.  Stream-ordered
+ * on `stream`, no synchronisation, no atomics; it does not use the handle's slices.  Results do not depend on B or on a world's place
+ * in the batch.  No gradients flow through the solve (the reference has none). */
+typedef struct {
+  double convergence_threshold;   /* 1e-7 */
+  int32_t max_step_count;         /* 100; IKMapping::setPositions passes 500 */
+  double least_squares_damping;   /* 0.01 */
+  int32_t start_clamped;          /* 0 */
+  int32_t line_search;            /* 1 */
+  int32_t dont_exit_transpose;    /* 0 */
+} nbl_ik_config;
+void nbl_ik_default_config(nbl_ik_config* config); /* math::IKConfig's defaults (IKSolver.hpp:31-38) */
+size_t nbl_ik_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B);
+int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* target, const double* q_init, const nbl_ik_config* config,
+                     double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream);
 
 /* enabled = 0: off (and reset); 1: HIP events around every kernel launch; N > 1: around the launches of every N-th forward /
  * backward call only (sampling keeps the perturbation of a timed region below 1 %). */

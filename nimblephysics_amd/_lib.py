@@ -130,6 +130,12 @@ def lib():
     L.nbl_inverse_dynamics_backward.restype = C.c_int32
     L.nbl_mass_matrix.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_size_t, vp]
     L.nbl_mass_matrix.restype = C.c_int32
+    L.nbl_ik_default_config.argtypes = [vp]
+    L.nbl_ik_default_config.restype = None
+    L.nbl_ik_workspace_bytes.argtypes = [vp, vp, C.c_int64]
+    L.nbl_ik_workspace_bytes.restype = C.c_size_t
+    L.nbl_ik_solve.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_ik_solve.restype = C.c_int32
     _lib = L
     return L
 
@@ -144,6 +150,7 @@ EXPORTED_SYMBOLS = [
     "nbl_model_max_contacts", "nbl_selftest_pinv_rows",
     "nbl_kin_map_create", "nbl_kin_map_destroy", "nbl_kin_map_dim", "nbl_kinematics_forward", "nbl_kinematics_backward",
     "nbl_dynamics_workspace_bytes", "nbl_inverse_dynamics_forward", "nbl_inverse_dynamics_backward", "nbl_mass_matrix",
+    "nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve",
 ]
 
 

@@ -79,6 +79,9 @@
 #define nbl_inverse_dynamics_forward NBL_V(nbl_inverse_dynamics_forward)
 #define nbl_inverse_dynamics_backward NBL_V(nbl_inverse_dynamics_backward)
 #define nbl_mass_matrix NBL_V(nbl_mass_matrix)
+#define nbl_ik_default_config NBL_V(nbl_ik_default_config)
+#define nbl_ik_workspace_bytes NBL_V(nbl_ik_workspace_bytes)
+#define nbl_ik_solve NBL_V(nbl_ik_solve)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

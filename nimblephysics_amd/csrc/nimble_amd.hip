@@ -27,6 +27,7 @@
 #include "inertia_backward.hip"
 #include "kinematics.hip"
 #include "dynamics.hip"
+#include "ik.hip"
 
 using namespace NBL_NS;
 
@@ -1787,6 +1788,53 @@ int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M,
   HIP_TRY(hipMemsetAsync(M, 0, sizeof(double) * (size_t)m->n * m->n * (size_t)B, (hipStream_t)stream));   // unrelated DOFs: the kernel writes the rest
   hipLaunchKernelGGL(k_mass_matrix, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
                      (const DevBody*)m->dBodies, m->mdl, B, state, M, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// ---- batched inverse kinematics (IKMapping::setPositions = math::solveIK with one restart; csrc/ik.hip) ---------------------------------
+void nbl_ik_default_config(nbl_ik_config* c) {   // math::IKConfig (IKSolver.hpp:31-38)
+  if (!c) return;
+  c->convergence_threshold = 1e-7; c->max_step_count = 100; c->least_squares_damping = 0.01;
+  c->start_clamped = 0; c->line_search = 1; c->dont_exit_transpose = 0;
+}
+
+size_t nbl_ik_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) {
+  if (!m || !k || B <= 0) return 0;
+  return sizeof(double) * (size_t)ikLayout(m->n, k->P).total * (size_t)B;
+}
+
+int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* target, const double* q_init, const nbl_ik_config* config,
+                     double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!m || !k) return fail(NBL_E_BADARG, "null argument");
+  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  IkConfig cfg;
+  if (config) {
+    cfg.convergenceThreshold = config->convergence_threshold; cfg.maxStepCount = config->max_step_count;
+    cfg.damping = config->least_squares_damping; cfg.startClamped = config->start_clamped ? 1 : 0;
+    cfg.lineSearch = config->line_search ? 1 : 0; cfg.dontExitTranspose = config->dont_exit_transpose ? 1 : 0;
+  } else {   // IKMapping::setPositions: IKConfig().setMaxStepCount(500)
+    cfg.convergenceThreshold = 1e-7; cfg.maxStepCount = 500; cfg.damping = 0.01; cfg.startClamped = 0; cfg.lineSearch = 1; cfg.dontExitTranspose = 0;
+  }
+  if (cfg.maxStepCount < 1) return fail(NBL_E_BADARG, "max_step_count must be at least 1 (got " + std::to_string(cfg.maxStepCount) + ")");
+  if (cfg.maxStepCount > IK_MAX_STEP_COUNT)
+    return fail(NBL_E_BADARG, "max_step_count above " + std::to_string(IK_MAX_STEP_COUNT) + " (got " + std::to_string(cfg.maxStepCount) +
+                                  "): a lane runs its world's whole solve in one launch");
+  if (!(cfg.damping >= 0.0) || !(cfg.convergenceThreshold >= 0.0)) return fail(NBL_E_BADARG, "least_squares_damping and convergence_threshold must not be negative");
+  if (cfg.damping == 0.0)
+    return fail(NBL_E_UNSUPPORTED, "least_squares_damping = 0 (the reference's complete orthogonal decomposition) is outside the device path");
+  if (B == 0) return NBL_OK;
+  if (!target || !q_out || !workspace) return fail(NBL_E_BADARG, "null argument");
+  if ((B + IK_BLOCK - 1) / IK_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  const size_t need = nbl_ik_workspace_bytes(m, k, B);
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "IK workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_ik_workspace_bytes() = " + std::to_string(need));
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_ik_solve, dim3((unsigned)((B + IK_BLOCK - 1) / IK_BLOCK)), dim3(IK_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
+                     m->nb, m->n, k->P, B, target, q_init, cfg, q_out, loss, steps, (double*)workspace);
   HIP_TRY(hipGetLastError());
   return NBL_OK;
 }

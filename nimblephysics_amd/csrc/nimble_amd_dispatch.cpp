@@ -73,7 +73,11 @@
   int32_t nbl_inverse_dynamics_forward##S(void*, int64_t, const double*, const double*, int32_t, double*, void*, size_t, void*);           \
   int32_t nbl_inverse_dynamics_backward##S(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, \
                                            void*, size_t, void*);                                                                          \
-  int32_t nbl_mass_matrix##S(void*, int64_t, const double*, double*, void*, size_t, void*);
+  int32_t nbl_mass_matrix##S(void*, int64_t, const double*, double*, void*, size_t, void*);                                                \
+  void nbl_ik_default_config##S(nbl_ik_config*);                                                                                           \
+  size_t nbl_ik_workspace_bytes##S(const void*, const void*, int64_t);                                                                     \
+  int32_t nbl_ik_solve##S(void*, const void*, int64_t, const double*, const double*, const nbl_ik_config*, double*, double*, int32_t*,     \
+                          void*, size_t, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -133,6 +137,8 @@ struct Variant {
   int32_t (*inverse_dynamics_forward)(void*, int64_t, const double*, const double*, int32_t, double*, void*, size_t, void*);
   int32_t (*inverse_dynamics_backward)(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, void*, size_t, void*);
   int32_t (*mass_matrix)(void*, int64_t, const double*, double*, void*, size_t, void*);
+  size_t (*ik_workspace_bytes)(const void*, const void*, int64_t);
+  int32_t (*ik_solve)(void*, const void*, int64_t, const double*, const double*, const nbl_ik_config*, double*, double*, int32_t*, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -144,7 +150,7 @@ struct Variant {
    nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
    nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_kin_map_create##S, nbl_kin_map_destroy##S, nbl_kin_map_dim##S,          \
    nbl_kinematics_forward##S, nbl_kinematics_backward##S, nbl_dynamics_workspace_bytes##S, nbl_inverse_dynamics_forward##S,                 \
-   nbl_inverse_dynamics_backward##S, nbl_mass_matrix##S}
+   nbl_inverse_dynamics_backward##S, nbl_mass_matrix##S, nbl_ik_workspace_bytes##S, nbl_ik_solve##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -374,6 +380,17 @@ int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* sta
 }
 int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream) {
   return NBL_FWD(m, mass_matrix, B, state, M, workspace, workspace_bytes, stream);
+}
+
+void nbl_ik_default_config(nbl_ik_config* c) { nbl_ik_default_config_c8(c); }   // (the same in every instantiation)
+size_t nbl_ik_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) {
+  return (m && k && k->v == m->v) ? m->v->ik_workspace_bytes(m->impl, k->impl, B) : 0;
+}
+int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* target, const double* q_init, const nbl_ik_config* config,
+                     double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!k) return ownError(NBL_E_BADARG, "null kinematics map");
+  if (m && k->v != m->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model");
+  return NBL_FWD(m, ik_solve, k->impl, B, target, q_init, config, q_out, loss, steps, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -13,14 +13,17 @@ Differences from the reference, all forced by batching or by this library's mode
   * `state` is `[..., 2n]` (`[2n]` gives `[P]`, exactly the reference; `[B, 2n]` gives `[B, P]`; `[B, T+1, 2n]` - what `rollout()`
     returns - gives `[B, T+1, P]`); CPU float64 tensors come back as CPU tensors, device tensors stay on the device;
   * neither function changes the World's state (the reference's layers call world.setState).
-What stays out: COM entries (no public constructor in the reference), the IK setters (setPositions runs an IK solve), IdentityMapping,
-MappedBackpropSnapshot and world.addMapping.
+The setters (IKMapping.cpp:86-135): `setPositions` runs the batched inverse-kinematics solve of csrc/ik.hip (`solve_ik`: the reference's
+math::solveIK with one restart, one world per lane, no autograd - the reference has none), `setVelocities` applies the pseudo-inverse of
+the velocity Jacobian, `setControlForces` its transpose.
+What stays out: COM entries (no public constructor in the reference), IdentityMapping, MappedBackpropSnapshot and world.addMapping.
 """
 from __future__ import annotations
 
 import ctypes as C
 import re
-from typing import List, Tuple, Union
+from dataclasses import dataclass
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -193,9 +196,169 @@ class IKMapping:
         """IKMapping::getRealVelToMappedVelJac = getVelJacobian (IKMapping.cpp:429-473): [B, P, n], dense."""
         return self._dense(world, 1)
 
+    # ---- the reference's setters on the World's current state (IKMapping.cpp:86-135) ----
+    def setPositions(self, world, positions: torch.Tensor):
+        """IKMapping::setPositions: solve for joint positions whose mapped positions are `positions` ([B, P], or [P] for a state set as
+        one 1-D vector) - from ZERO with 500 steps, like the reference - and write them into the position block of the World's state.
+        The velocities are kept; the coordinates of immobile skeletons stay zero."""
+        s = self._current(world)
+        q_soa, _, _ = _solve_ik_soa(world, self, _targets_soa(world, self, positions, s.shape[1], "IKMapping.setPositions"), None, None)
+        s[:world.n].copy_(q_soa)      # in place: world._state is the World's own tensor (to_soa allocates it fresh in setState / step)
+
+    def _dense_device(self, world, block: int) -> torch.Tensor:
+        """_dense over the device's coordinates, always [B, P, n]"""
+        J = self._dense(world, block)
+        if getattr(world, "_one_d", False):
+            J = J.unsqueeze(0)
+        lay = world.ref_layout
+        return J if lay is None else J.index_select(2, lay._idx(world.device, "mobile"))
+
+    def setVelocities(self, world, velocities: torch.Tensor):
+        """IKMapping::setVelocities: v = pinv(Jvel) velocities (getVelJacobianInverse, IKMapping.cpp:122-127) into the velocity block of
+        the World's state; the positions are kept."""
+        s = self._current(world)
+        w_soa = _targets_soa(world, self, velocities, s.shape[1], "IKMapping.setVelocities")          # [P][B]
+        v = torch.linalg.pinv(self._dense_device(world, 1)) @ w_soa.t().unsqueeze(-1)               # [B, n, 1]
+        s[world.n:].copy_(v.squeeze(-1).t())
+
+    def setControlForces(self, world, forces: torch.Tensor):
+        """IKMapping::setControlForces: tau = Jvel^T forces (IKMapping.cpp:130-135) through the kinematics VJP, restricted to the World's
+        action space (World.setAction's vector)."""
+        s = self._current(world)
+        f_soa = _targets_soa(world, self, forces, s.shape[1], "IKMapping.setControlForces")
+        gs = self._backward_soa(world, s, None, f_soa)
+        cols = torch.tensor(list(world.model.action_map), dtype=torch.long, device=world.device)
+        world._action = gs[world.n:].index_select(0, cols).contiguous()
+
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# ---- batched inverse kinematics (csrc/ik.hip) ------------------------------------------------------------------------------------------
+@dataclass
+class IKConfig:
+    """math::IKConfig (dart/math/IKSolver.hpp:15-42) without the restart and logging fields: one restart, as IKMapping::setPositions runs
+    it.  The defaults are the reference's; setPositions itself uses max_step_count = 500."""
+    convergence_threshold: float = 1e-7
+    max_step_count: int = 100
+    least_squares_damping: float = 0.01
+    start_clamped: bool = False
+    line_search: bool = True
+    dont_exit_transpose: bool = False
+
+    def setConvergenceThreshold(self, v):
+        self.convergence_threshold = float(v); return self
+
+    def setMaxStepCount(self, v):
+        self.max_step_count = int(v); return self
+
+    def setLeastSquaresDamping(self, v):
+        self.least_squares_damping = float(v); return self
+
+    def setStartClamped(self, v):
+        self.start_clamped = bool(v); return self
+
+    def setLineSearch(self, v):
+        self.line_search = bool(v); return self
+
+    def setDontExitTranspose(self, v):
+        self.dont_exit_transpose = bool(v); return self
+
+
+class _CIKConfig(C.Structure):       # nbl_ik_config
+    _fields_ = [("convergence_threshold", C.c_double), ("max_step_count", C.c_int32), ("least_squares_damping", C.c_double),
+                ("start_clamped", C.c_int32), ("line_search", C.c_int32), ("dont_exit_transpose", C.c_int32)]
+
+
+# The solver's scratch is 3 n + P + min(P, n) + P n + min(P, n)^2 doubles per world (IkLayout, csrc/ik_dev.hpp: 7.9 kB on Atlas-20 with four spatial entries, 230 kB at the
+# caps P = 384, n = 64): a batch whose scratch would pass this many bytes is cut into launches of whole wavefronts (the results do not
+# depend on the cut: a world's solve does not depend on the batch).
+IK_WORKSPACE_BYTES = 1 << 30
+
+
+def _targets_soa(world, mapping: "IKMapping", t: torch.Tensor, B_expected: Optional[int], what: str) -> torch.Tensor:
+    P = mapping.getPosDim()
+    x = t.detach()
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dim() != 2 or x.shape[1] != P:
+        raise ValueError(f"{what}: expected [B, {P}] (or [{P}]) mapped values; got {tuple(t.shape)}")
+    if B_expected is not None and x.shape[0] != B_expected:
+        raise ValueError(f"{what}: {x.shape[0]} worlds given, the World's state holds {B_expected}")
+    if P == 0:
+        return torch.zeros((0, x.shape[0]), dtype=torch.float64, device=world.device)
+    return world.to_soa(world._prep(x, P, "ik_target"))
+
+
+def _solve_ik_soa(world, mapping: "IKMapping", t_soa: torch.Tensor, init_soa, config: Optional[IKConfig]):
+    """target [P][B], init [n][B] or None -> (q [n][B], loss [B], steps [B] int32) on the World's device"""
+    _join_if_deferred(world)
+    P, B, n = mapping.getPosDim(), t_soa.shape[1], world.n
+    q = torch.empty((n, B), dtype=torch.float64, device=world.device)
+    loss = torch.empty((B,), dtype=torch.float64, device=world.device)
+    steps = torch.empty((B,), dtype=torch.int32, device=world.device)
+    if P == 0:
+        raise ValueError("solve_ik: the mapping has no entries")
+    cfg = None
+    if config is not None:
+        cfg = _CIKConfig(config.convergence_threshold, config.max_step_count, config.least_squares_damping, int(config.start_clamped),
+                         int(config.line_search), int(config.dont_exit_transpose))
+    if B == 0:
+        return q, loss, steps
+    km = mapping._device_map(world)
+    L = world._L
+    per = L.nbl_ik_workspace_bytes(world._h, km, 1)
+    chunk = max(64, (IK_WORKSPACE_BYTES // max(per, 1)) // 64 * 64)
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        whole = b0 == 0 and b1 == B
+        tc = t_soa if whole else t_soa[:, b0:b1].contiguous()
+        ic = init_soa if (whole or init_soa is None) else init_soa[:, b0:b1].contiguous()
+        qc = q if whole else torch.empty((n, b1 - b0), dtype=torch.float64, device=world.device)
+        need = L.nbl_ik_workspace_bytes(world._h, km, b1 - b0)
+        ws = getattr(world, "_ik_ws", None)
+        if ws is None or ws.numel() < need or ws.device != world.device:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=world.device)
+            world._ik_ws = ws
+        check(L.nbl_ik_solve(world._h, km, b1 - b0, _ptr(tc), _ptr(ic), C.byref(cfg) if cfg is not None else None, _ptr(qc),
+                             _ptr(loss[b0:b1]), _ptr(steps[b0:b1]), _ptr(ws), ws.numel(), world._stream()), "nbl_ik_solve")
+        if not whole:
+            q[:, b0:b1] = qc
+    return q, loss, steps
+
+
+def solve_ik(world, map: "IKMapping", targets: torch.Tensor, init: Optional[torch.Tensor] = None, config: Optional[IKConfig] = None):
+    """Batched inverse kinematics: joint positions whose mapped positions (`map_to_pos`) meet `targets`, by the reference's
+    math::solveIK with one restart (20 steps of refineIK, then config.max_step_count steps; IKSolver.cpp:195-493), one world per lane of
+    csrc/ik.hip.  targets [B, P] or [P]; init [B, n] / [n] (None: zeros, as IKMapping::setPositions starts); config None: IKConfig()
+    (the reference's defaults, 100 steps).  Returns (q [B, n], loss [B] = |rows(q) - target|^2 at q, steps [B] int32 = evaluations
+    used); [P] gives q [n] and 0-d loss / steps.  CPU tensors come back as CPU tensors.  The World's state is left untouched; a World in
+    deferred-join mode is joined first.  No autograd: the reference has none either.  On a World with immobile skeletons q is over the
+    mobile coordinates (init may come in either layout)."""
+    _join_if_deferred(world)
+    one = targets.dim() == 1
+    t_soa = _targets_soa(world, map, targets, None, "solve_ik")
+    B = t_soa.shape[1]
+    init_soa = None
+    if init is not None:
+        x = init.detach()
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        lay = world.ref_layout
+        if lay is not None and x.shape[-1] == lay.n_ref:
+            x = x.index_select(-1, lay._idx(x.device, "mobile"))
+        if x.dim() != 2 or x.shape != (B, world.n):
+            raise ValueError(f"solve_ik: init has shape {tuple(init.shape)}; expected [{B}, {world.n}]")
+        init_soa = world.to_soa(world._prep(x, world.n, "ik_init"))
+    q_soa, loss, steps = _solve_ik_soa(world, map, t_soa, init_soa, config if config is not None else IKConfig())
+    q = world.from_soa(q_soa)
+    if targets.device.type == "cpu":
+        q, loss = world._to_host(q, loss)
+        steps = steps.cpu()
+    else:
+        q, loss, steps = q.to(targets.device), loss.to(targets.device), steps.to(targets.device)
+    return (q[0], loss[0], steps[0]) if one else (q, loss, steps)
 
 
 def _join_if_deferred(world):
