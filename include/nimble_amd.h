@@ -496,7 +496,7 @@ int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, c
  * state [2n][B] = [q; v], accel / tau / grad_* [n][B], M [n * n][B] (row-major n x n per world), device pointers, SoA like the step's.
  * B may be (T + 1) x worlds: a whole rollout in one launch.  workspace: device scratch of nbl_dynamics_workspace_bytes(m, B) bytes (one
  * size serves the three calls); calls that share a workspace must be ordered on one stream.  Stream-ordered, no synchronisation, no
- * atomics: bit-reproducible.  Not covered: the inverse mass matrix, external forces, Skeleton::getInverseDynamicsFromPredictions. */
+ * atomics: bit-reproducible.  Not covered: external forces on bodies and Skeleton::getInverseDynamicsFromPredictions. */
 #define NBL_ID_NO_VELOCITY 1  /* take v as 0 */
 #define NBL_ID_NO_GRAVITY 2   /* leave gravity out */
 #define NBL_ID_JOINT_FORCES 4 /* + damping v + spring (q - rest + dt v) per DOF: the terms nbl_step_forward puts on the right-hand side, so
@@ -514,6 +514,35 @@ int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* sta
                                       size_t workspace_bytes, void* stream);
 /* M(q): symmetric, both triangles written (M[i][j] and M[j][i] are the same bits).  Only the position block of state is read. */
 int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- forward dynamics and the inverse mass matrix (csrc/dynamics.hip) ---------------------------------------------------------------------
+ * a = M(q)^-1 (tau - C(q, v))  by the articulated-body algorithm (Skeleton::computeForwardDynamics, Skeleton.cpp:13296-13314) and
+ * Y = M(q)^-1 X  /  M(q)^-1 itself (World::getInvMassMatrix; the recursion of Skeleton::updateInvMassMatrix, Skeleton.cpp:12573-12660)
+ * of B worlds, one world per lane: O(n) per right-hand side, M is never formed.  The flags are the NBL_ID_* of inverse dynamics, and under
+ * the same flags nbl_forward_dynamics_forward and nbl_inverse_dynamics_forward are inverse functions of each other (with
+ * NBL_ID_JOINT_FORCES the right-hand side carries - damping v - spring (q - rest + dt v) exactly as nbl_step_forward has it: a is then
+ * (v' - v) / dt of a contact-free step).  Conventions as for the nbl_inverse_dynamics_* calls: device pointers, SoA, state [2n][B],
+ * tau / accel / grad_* [n][B], B may be (T + 1) x worlds, the handle's CURRENT inertias are read, the handle's slices are not used,
+ * stream-ordered, no synchronisation, no atomics, bit-reproducible and independent of B and of a world's place in the batch.
+ * workspace: nbl_forward_dynamics_workspace_bytes(m, B) bytes of device scratch (84 doubles per body and world, plus 2 n per world for the
+ * reverse pass; one size serves the four calls); calls that share a workspace must be ordered on one stream.
+ * Errors: NBL_E_BADARG (null handle / state / output / workspace, B < 0, R < 1, unknown flag bits), NBL_E_WORKSPACE (workspace too small);
+ * nothing is launched then.  B = 0 is a no-op. */
+size_t nbl_forward_dynamics_workspace_bytes(const nbl_model* m, int64_t B);
+/* accel = M(q)^-1 (tau - C(q, v)).  tau NULL: 0. */
+int32_t nbl_forward_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, double* accel,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+/* The exact reverse pass, two launches: a is recomputed and lambda = M^-1 grad_accel; grad_tau [n][B] = (accumulate: +=) lambda;
+ * grad_state [2n][B] = (+=) -(d ID / d [q; v])^T lambda at (q, v, a) under the same flags, through the reverse kernel of
+ * nbl_inverse_dynamics_backward.  Either output may be NULL. */
+int32_t nbl_forward_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, const double* grad_accel,
+                                      double* grad_state, double* grad_tau, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+/* Y [R][n][B] = M(q)^-1 X [R][n][B]: the articulated inertias once per world, two sweeps per right-hand side.  Only the position block of
+ * state is read.  X NULL with R = n: the identity (nothing is read) - nbl_inv_mass_matrix. */
+int32_t nbl_inv_mass_apply(nbl_model* m, int64_t B, int32_t R, const double* state, const double* X, double* Y, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* Minv [n * n][B] (row-major n x n per world) = M(q)^-1: one triangle is computed and mirrored, Minv[i][j] and Minv[j][i] are the same bits. */
+int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- batched inverse kinematics (csrc/ik.hip) --------------------------------------------------------------------------------------------
  * IKMapping::setPositions (dart/neural/IKMapping.cpp:86-119) for B independent worlds: find joint positions whose mapped rows (the rows
  * of nbl_kinematics_forward) meet `target`.  The kernel restates math::solveIK with ONE restart and math::refineIK

@@ -21,6 +21,10 @@ NBL_E_HIP = -3
 NBL_E_WORKSPACE = -4
 NBL_E_NOGPU = -5
 
+ID_NO_VELOCITY = 1   # NBL_ID_*: the flags of the inverse- and forward-dynamics calls
+ID_NO_GRAVITY = 2
+ID_JOINT_FORCES = 4
+
 ST_CONTACT = 0x1
 ST_LCP_STAGE0 = 0x2
 ST_LCP_PIVOT = 0x4

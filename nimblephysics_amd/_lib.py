@@ -130,6 +130,16 @@ def lib():
     L.nbl_inverse_dynamics_backward.restype = C.c_int32
     L.nbl_mass_matrix.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_size_t, vp]
     L.nbl_mass_matrix.restype = C.c_int32
+    L.nbl_forward_dynamics_workspace_bytes.argtypes = [vp, C.c_int64]
+    L.nbl_forward_dynamics_workspace_bytes.restype = C.c_size_t
+    L.nbl_forward_dynamics_forward.argtypes = [vp, C.c_int64, vp, vp, C.c_int32, vp, vp, C.c_size_t, vp]
+    L.nbl_forward_dynamics_forward.restype = C.c_int32
+    L.nbl_forward_dynamics_backward.argtypes = [vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_forward_dynamics_backward.restype = C.c_int32
+    L.nbl_inv_mass_apply.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_inv_mass_apply.restype = C.c_int32
+    L.nbl_inv_mass_matrix.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_inv_mass_matrix.restype = C.c_int32
     L.nbl_ik_default_config.argtypes = [vp]
     L.nbl_ik_default_config.restype = None
     L.nbl_ik_workspace_bytes.argtypes = [vp, vp, C.c_int64]
@@ -150,6 +160,7 @@ EXPORTED_SYMBOLS = [
     "nbl_model_max_contacts", "nbl_selftest_pinv_rows",
     "nbl_kin_map_create", "nbl_kin_map_destroy", "nbl_kin_map_dim", "nbl_kinematics_forward", "nbl_kinematics_backward",
     "nbl_dynamics_workspace_bytes", "nbl_inverse_dynamics_forward", "nbl_inverse_dynamics_backward", "nbl_mass_matrix",
+    "nbl_forward_dynamics_workspace_bytes", "nbl_forward_dynamics_forward", "nbl_forward_dynamics_backward", "nbl_inv_mass_apply", "nbl_inv_mass_matrix",
     "nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve",
 ]
 

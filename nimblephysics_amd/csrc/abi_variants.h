@@ -79,6 +79,11 @@
 #define nbl_inverse_dynamics_forward NBL_V(nbl_inverse_dynamics_forward)
 #define nbl_inverse_dynamics_backward NBL_V(nbl_inverse_dynamics_backward)
 #define nbl_mass_matrix NBL_V(nbl_mass_matrix)
+#define nbl_forward_dynamics_workspace_bytes NBL_V(nbl_forward_dynamics_workspace_bytes)
+#define nbl_forward_dynamics_forward NBL_V(nbl_forward_dynamics_forward)
+#define nbl_forward_dynamics_backward NBL_V(nbl_forward_dynamics_backward)
+#define nbl_inv_mass_apply NBL_V(nbl_inv_mass_apply)
+#define nbl_inv_mass_matrix NBL_V(nbl_inv_mass_matrix)
 #define nbl_ik_default_config NBL_V(nbl_ik_default_config)
 #define nbl_ik_workspace_bytes NBL_V(nbl_ik_workspace_bytes)
 #define nbl_ik_solve NBL_V(nbl_ik_solve)

@@ -1,6 +1,7 @@
-// dynamics.hip — joint-space dynamics quantities for B worlds (nbl_inverse_dynamics_forward / _backward, nbl_mass_matrix): the device side
-// of Skeleton::getInverseDynamics, World::getCoriolisAndGravityForces and World::getMassMatrix and of their vector-Jacobian products
-// (nimblephysics_amd/dynamics.py).  The math is in dynamics_dev.hpp.
+// dynamics.hip — joint-space dynamics quantities for B worlds (nbl_inverse_dynamics_forward / _backward, nbl_mass_matrix,
+// nbl_forward_dynamics_forward / _backward, nbl_inv_mass_apply, nbl_inv_mass_matrix): the device side of Skeleton::getInverseDynamics,
+// World::getCoriolisAndGravityForces, World::getMassMatrix, Skeleton::computeForwardDynamics and World::getInvMassMatrix and of their
+// vector-Jacobian products (nimblephysics_amd/dynamics.py).  The math is in dynamics_dev.hpp.
 //
 // ONE WORLD PER LANE, like k_step_forward's Ctx path and the kinematics kernels: the body constants are wave-uniform (scalar loads), and
 // the per-body T / V / A / F and their adjoints, which must survive between the two tree sweeps, live in the caller's workspace laid out
@@ -38,6 +39,36 @@ __global__ __launch_bounds__(DYN_BLOCK) void k_mass_matrix(const DevBody* __rest
   const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
   if (b >= B) return;
   massMatrixWorld(bodies, mdl.nb, mdl.n, B, b, state, M, ws);
+}
+
+// a = M(q)^-1 (tau - C(q, v)): the articulated-body algorithm's three sweeps on the [body][FD_SLOTS][B] workspace.
+__global__ __launch_bounds__(DYN_BLOCK) void k_forward_dynamics(const DevBody* __restrict__ bodies, const DevDof* __restrict__ dofs, DevModel mdl,
+                                                                int flags, int64_t B, const double* __restrict__ state,
+                                                                const double* __restrict__ tau, double* __restrict__ accel, double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  fdForwardWorld(bodies, dofs, mdl.nb, mdl.n, mdl.gravity, mdl.dt, flags, B, b, state, tau, accel, ws);
+}
+
+// First launch of nbl_forward_dynamics_backward: a again, lambda = M^-1 grad_accel, grad_tau (+)= lambda, neglam = -lambda; the second
+// launch is k_inverse_dynamics_vjp at (q, v, a) with the cotangent neglam.
+__global__ __launch_bounds__(DYN_BLOCK) void k_forward_dynamics_lambda(const DevBody* __restrict__ bodies, const DevDof* __restrict__ dofs,
+                                                                       DevModel mdl, int flags, int64_t B, const double* __restrict__ state,
+                                                                       const double* __restrict__ tau, const double* __restrict__ gaccel,
+                                                                       double* __restrict__ accel, double* __restrict__ neglam,
+                                                                       double* __restrict__ gtau, int accumulate, double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  fdLambdaWorld(bodies, dofs, mdl.nb, mdl.n, mdl.gravity, mdl.dt, flags, B, b, state, tau, gaccel, accel, neglam, gtau, accumulate, ws);
+}
+
+// Y [R][n][B] = M(q)^-1 X [R][n][B];  X null (R = n): Y = M(q)^-1 itself, [n * n][B], both triangles from one computation.
+__global__ __launch_bounds__(DYN_BLOCK) void k_minv_apply(const DevBody* __restrict__ bodies, DevModel mdl, int64_t B, int R,
+                                                          const double* __restrict__ state, const double* __restrict__ X, double* __restrict__ Y,
+                                                          double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  minvApplyWorld(bodies, mdl.nb, mdl.n, B, b, state, R, X, Y, ws);
 }
 
 }  // namespace NBL_NS

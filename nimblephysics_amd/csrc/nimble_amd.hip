@@ -1792,6 +1792,88 @@ int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M,
   return NBL_OK;
 }
 
+// ---- forward dynamics and the inverse mass matrix (articulated-body algorithm; csrc/dynamics.hip) ---------------------------------------
+// workspace: [nb][FD_SLOTS][B] tree slots (the reverse pass's k_inverse_dynamics_vjp reuses them: DYN_SLOTS <= FD_SLOTS), then the
+// recomputed acceleration [n][B] and -lambda [n][B] of nbl_forward_dynamics_backward
+static_assert(DYN_SLOTS <= FD_SLOTS, "the reverse pass runs k_inverse_dynamics_vjp on the forward-dynamics tree slots");
+size_t nbl_forward_dynamics_workspace_bytes(const nbl_model* m, int64_t B) {
+  if (!m || B <= 0) return 0;
+  return sizeof(double) * ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
+}
+
+static int32_t fdynCheck(const nbl_model* m, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (B == 0) return NBL_OK;
+  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
+  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  const size_t need = nbl_forward_dynamics_workspace_bytes(m, B);
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "forward-dynamics workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_forward_dynamics_workspace_bytes() = " + std::to_string(need));
+  return NBL_OK;
+}
+
+int32_t nbl_forward_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, double* accel,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  int32_t rc = fdynCheck(m, B, state, accel, workspace, workspace_bytes);
+  if (rc == NBL_OK) rc = dynFlags(flags);
+  if (rc != NBL_OK || B == 0) return rc;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_forward_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, accel, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_forward_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, const double* grad_accel,
+                                      double* grad_state, double* grad_tau, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  int32_t rc = fdynCheck(m, B, state, grad_accel, workspace, workspace_bytes);
+  if (rc == NBL_OK) rc = dynFlags(flags);
+  if (rc != NBL_OK || B == 0) return rc;
+  if (!grad_state && !grad_tau) return NBL_OK;
+  DeviceGuard guard(m->device);
+  double* ws = (double*)workspace;
+  double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
+  double* neglam = accel + (size_t)m->n * (size_t)B;
+  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
+  hipLaunchKernelGGL(k_forward_dynamics_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
+                     m->mdl, (int)flags, B, state, tau, grad_accel, accel, neglam, grad_tau, accumulate ? 1 : 0, ws);
+  HIP_TRY(hipGetLastError());
+  if (grad_state) {   // grad_state (+)= -(d ID / d [q; v])^T lambda at (q, v, a): inverse dynamics is the exact inverse function
+    hipLaunchKernelGGL(k_inverse_dynamics_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
+                       m->mdl, (int)flags, B, state, (const double*)accel, (const double*)neglam, grad_state, (double*)nullptr, accumulate ? 1 : 0, ws);
+    HIP_TRY(hipGetLastError());
+  }
+  return NBL_OK;
+}
+
+int32_t nbl_inv_mass_apply(nbl_model* m, int64_t B, int32_t R, const double* state, const double* X, double* Y, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  const int32_t rc = fdynCheck(m, B, state, Y, workspace, workspace_bytes);
+  if (rc != NBL_OK) return rc;
+  if (R < 1) return fail(NBL_E_BADARG, "R must be at least 1 (got " + std::to_string(R) + ")");
+  if (B == 0) return NBL_OK;
+  if (!X && R != m->n) return fail(NBL_E_BADARG, "X may be null (the identity) only with R = n");
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, m->mdl, B, (int)R, state, X, Y, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = fdynCheck(m, B, state, Minv, workspace, workspace_bytes);
+  if (rc != NBL_OK || B == 0) return rc;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, m->mdl, B, (int)m->n, state, (const double*)nullptr, Minv, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
 // ---- batched inverse kinematics (IKMapping::setPositions = math::solveIK with one restart; csrc/ik.hip) ---------------------------------
 void nbl_ik_default_config(nbl_ik_config* c) {   // math::IKConfig (IKSolver.hpp:31-38)
   if (!c) return;

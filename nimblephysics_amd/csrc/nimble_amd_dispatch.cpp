@@ -74,6 +74,12 @@
   int32_t nbl_inverse_dynamics_backward##S(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, \
                                            void*, size_t, void*);                                                                          \
   int32_t nbl_mass_matrix##S(void*, int64_t, const double*, double*, void*, size_t, void*);                                                \
+  size_t nbl_forward_dynamics_workspace_bytes##S(const void*, int64_t);                                                                    \
+  int32_t nbl_forward_dynamics_forward##S(void*, int64_t, const double*, const double*, int32_t, double*, void*, size_t, void*);           \
+  int32_t nbl_forward_dynamics_backward##S(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, \
+                                           void*, size_t, void*);                                                                          \
+  int32_t nbl_inv_mass_apply##S(void*, int64_t, int32_t, const double*, const double*, double*, void*, size_t, void*);                     \
+  int32_t nbl_inv_mass_matrix##S(void*, int64_t, const double*, double*, void*, size_t, void*);                                            \
   void nbl_ik_default_config##S(nbl_ik_config*);                                                                                           \
   size_t nbl_ik_workspace_bytes##S(const void*, const void*, int64_t);                                                                     \
   int32_t nbl_ik_solve##S(void*, const void*, int64_t, const double*, const double*, const nbl_ik_config*, double*, double*, int32_t*,     \
@@ -139,6 +145,11 @@ struct Variant {
   int32_t (*mass_matrix)(void*, int64_t, const double*, double*, void*, size_t, void*);
   size_t (*ik_workspace_bytes)(const void*, const void*, int64_t);
   int32_t (*ik_solve)(void*, const void*, int64_t, const double*, const double*, const nbl_ik_config*, double*, double*, int32_t*, void*, size_t, void*);
+  size_t (*forward_dynamics_workspace_bytes)(const void*, int64_t);
+  int32_t (*forward_dynamics_forward)(void*, int64_t, const double*, const double*, int32_t, double*, void*, size_t, void*);
+  int32_t (*forward_dynamics_backward)(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, void*, size_t, void*);
+  int32_t (*inv_mass_apply)(void*, int64_t, int32_t, const double*, const double*, double*, void*, size_t, void*);
+  int32_t (*inv_mass_matrix)(void*, int64_t, const double*, double*, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -150,7 +161,9 @@ struct Variant {
    nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
    nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_kin_map_create##S, nbl_kin_map_destroy##S, nbl_kin_map_dim##S,          \
    nbl_kinematics_forward##S, nbl_kinematics_backward##S, nbl_dynamics_workspace_bytes##S, nbl_inverse_dynamics_forward##S,                 \
-   nbl_inverse_dynamics_backward##S, nbl_mass_matrix##S, nbl_ik_workspace_bytes##S, nbl_ik_solve##S}
+   nbl_inverse_dynamics_backward##S, nbl_mass_matrix##S, nbl_ik_workspace_bytes##S, nbl_ik_solve##S,                        \
+   nbl_forward_dynamics_workspace_bytes##S, nbl_forward_dynamics_forward##S, nbl_forward_dynamics_backward##S, nbl_inv_mass_apply##S,       \
+   nbl_inv_mass_matrix##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -380,6 +393,25 @@ int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* sta
 }
 int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream) {
   return NBL_FWD(m, mass_matrix, B, state, M, workspace, workspace_bytes, stream);
+}
+
+size_t nbl_forward_dynamics_workspace_bytes(const nbl_model* m, int64_t B) { return m ? m->v->forward_dynamics_workspace_bytes(m->impl, B) : 0; }
+int32_t nbl_forward_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, double* accel,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return NBL_FWD(m, forward_dynamics_forward, B, state, tau, flags, accel, workspace, workspace_bytes, stream);
+}
+int32_t nbl_forward_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, const double* grad_accel,
+                                      double* grad_state, double* grad_tau, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return NBL_FWD(m, forward_dynamics_backward, B, state, tau, flags, grad_accel, grad_state, grad_tau, accumulate, workspace, workspace_bytes,
+                 stream);
+}
+int32_t nbl_inv_mass_apply(nbl_model* m, int64_t B, int32_t R, const double* state, const double* X, double* Y, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return NBL_FWD(m, inv_mass_apply, B, R, state, X, Y, workspace, workspace_bytes, stream);
+}
+int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream) {
+  return NBL_FWD(m, inv_mass_matrix, B, state, Minv, workspace, workspace_bytes, stream);
 }
 
 void nbl_ik_default_config(nbl_ik_config* c) { nbl_ik_default_config_c8(c); }   // (the same in every instantiation)

@@ -1,10 +1,21 @@
 """Joint-space dynamics quantities for batches of states: `inverse_dynamics`, `coriolis_and_gravity`, `mass_matrix`
 (Skeleton::getInverseDynamics, dart/dynamics/Skeleton.cpp:9658-9666; World::getCoriolisAndGravityForces and World::getMassMatrix,
-dart/simulation/World.cpp:1943-1986), with exact gradients.
+dart/simulation/World.cpp:1943-1986), and their counterparts `forward_dynamics`, `multiply_by_inv_mass_matrix`, `inv_mass_matrix`
+(Skeleton::computeForwardDynamics, Skeleton.cpp:13296-13314; World::getInvMassMatrix), with exact gradients.
 
     tau = inverse_dynamics(world, state, accel)        [..., 2n], [..., n] -> [..., n]      tau = M(q) a + C(q, v)
     C   = coriolis_and_gravity(world, state)           [..., 2n] -> [..., n]                 inverse_dynamics with a = 0
     M   = mass_matrix(world, state)                    [..., 2n] -> [..., n, n]
+    a   = forward_dynamics(world, state, tau)          [..., 2n], [..., n] -> [..., n]      a = M(q)^-1 (tau - C(q, v))
+    y   = multiply_by_inv_mass_matrix(world, state, x) [..., 2n], [..., n] or [..., n, R] -> the shape of x:  y = M(q)^-1 x
+    Mi  = inv_mass_matrix(world, state)                [..., 2n] -> [..., n, n]
+
+The last three run the articulated-body recursion (O(n) per right-hand side; M is never formed) and are the inverse functions of the
+first three: forward_dynamics(s, inverse_dynamics(s, a)) = a under the same `joint_forces`.  Their backward passes need no new theory:
+lambda = M^-1 (cotangent) by the same recursion, the cotangent of tau / x is lambda, and the state receives -(d ID / d state)^T lambda
+(-(d (M y) / dq)^T lambda for the M^-1 products) through the reverse kernel of inverse dynamics.  On a world with immobile skeletons a
+`state` in the reference's layout gives THESE three outputs in the reference's layout too: the frozen coordinates have zero acceleration,
+zero rows and columns in M^-1 (they cannot move, whatever acts on them) and zero gradient.
 
 Each is one launch of csrc/dynamics.hip over all the leading dimensions (`[2n]` is one world, `[B, 2n]` a batch, `[B, T+1, 2n]` - what
 `rollout()` returns - a whole trajectory), differentiable with respect to `state` and `accel`: recursive Newton-Euler with its exact
@@ -21,8 +32,7 @@ layout is restricted to the mobile coordinates as map_to_pos does; the outputs a
 frozen entries are zero.  The reference's own mass matrix has blocks for the immobile skeletons (their bodies keep their masses there),
 which this model - it welded them to the world - cannot give.
 
-Out of scope: the inverse mass matrix (World::getInvMassMatrix), external forces on bodies, and
-Skeleton::getInverseDynamicsFromPredictions.
+Out of scope: external forces on bodies (add J^T f from the kinematics VJP to tau) and Skeleton::getInverseDynamicsFromPredictions.
 """
 from __future__ import annotations
 
@@ -78,6 +88,76 @@ def mass_matrix_soa(world, s_soa: torch.Tensor) -> torch.Tensor:
         ws = _workspace(world, B)
         check(world._L.nbl_mass_matrix(world._h, B, _ptr(s_soa), _ptr(M), _ptr(ws), ws.numel(), world._stream()), "nbl_mass_matrix")
     return M
+
+
+def _fd_workspace(world, B: int):
+    """The scratch of the forward-dynamics / M^-1 calls (84 doubles per body and world), kept like _workspace."""
+    need = world._L.nbl_forward_dynamics_workspace_bytes(world._h, B)
+    ws = getattr(world, "_fdyn_ws", None)
+    if ws is None or ws.numel() < need or ws.device != world.device:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=world.device)
+        world._fdyn_ws = ws
+    return ws
+
+
+# ---- raw SoA calls: state [2n][B], tau / accel [n][B], X / Y [R][n][B], Minv [n * n][B] ----
+def forward_dynamics_soa(world, s_soa: torch.Tensor, t_soa, flags: int = 0) -> torch.Tensor:
+    B = s_soa.shape[1]
+    acc = torch.empty((world.n, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        ws = _fd_workspace(world, B)
+        check(world._L.nbl_forward_dynamics_forward(world._h, B, _ptr(s_soa), _ptr(t_soa), flags, _ptr(acc), _ptr(ws), ws.numel(), world._stream()),
+              "nbl_forward_dynamics_forward")
+    return acc
+
+
+def forward_dynamics_vjp_soa(world, s_soa: torch.Tensor, t_soa, g_soa: torch.Tensor, flags: int = 0, want_state: bool = True, want_tau: bool = True):
+    B = s_soa.shape[1]
+    gs = torch.empty((2 * world.n, B), dtype=torch.float64, device=world.device) if want_state else None
+    gt = torch.empty((world.n, B), dtype=torch.float64, device=world.device) if want_tau else None
+    if B > 0:
+        ws = _fd_workspace(world, B)
+        check(world._L.nbl_forward_dynamics_backward(world._h, B, _ptr(s_soa), _ptr(t_soa), flags, _ptr(g_soa), _ptr(gs), _ptr(gt), 0, _ptr(ws),
+                                                     ws.numel(), world._stream()), "nbl_forward_dynamics_backward")
+    return gs, gt
+
+
+def inv_mass_apply_soa(world, s_soa: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """X [R, n, B] -> M^-1 X [R, n, B]"""
+    R, _, B = X.shape
+    Y = torch.empty_like(X)
+    if B > 0:
+        ws = _fd_workspace(world, B)
+        check(world._L.nbl_inv_mass_apply(world._h, B, R, _ptr(s_soa), _ptr(X), _ptr(Y), _ptr(ws), ws.numel(), world._stream()), "nbl_inv_mass_apply")
+    return Y
+
+
+def inv_mass_matrix_soa(world, s_soa: torch.Tensor) -> torch.Tensor:
+    B = s_soa.shape[1]
+    Mi = torch.empty((world.n * world.n, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        ws = _fd_workspace(world, B)
+        check(world._L.nbl_inv_mass_matrix(world._h, B, _ptr(s_soa), _ptr(Mi), _ptr(ws), ws.numel(), world._stream()), "nbl_inv_mass_matrix")
+    return Mi
+
+
+def _minv_grad_q(world, s_soa: torch.Tensor, Y: torch.Tensor, Lam: torch.Tensor) -> torch.Tensor:
+    """-sum_r (d (M y_r) / dq)^T lambda_r, [n, B], of Y, Lam [R, n, B]: the reverse kernel of inverse dynamics over R x B worlds (world
+    (r, b): a = y_r, cotangent -lambda_r, no velocity, no gravity), cut into launches of whole right-hand sides above
+    MASS_BACKWARD_WORLDS like MassMatrixLayer.backward."""
+    R, n, B = Y.shape
+    per = max(1, min(R, MASS_BACKWARD_WORLDS // max(B, 1)))
+    gq = torch.zeros((n, B), dtype=torch.float64, device=world.device)
+    for r0 in range(0, R, per):
+        r1 = min(R, r0 + per)
+        rep = s_soa.repeat(1, r1 - r0)
+        acc = Y[r0:r1].permute(1, 0, 2).reshape(n, (r1 - r0) * B).contiguous()
+        cot = (-Lam[r0:r1]).permute(1, 0, 2).reshape(n, (r1 - r0) * B).contiguous()
+        gs, _ = inverse_dynamics_vjp_soa(world, rep, acc, cot, ID_NO_VELOCITY | ID_NO_GRAVITY, want_accel=False)
+        part = gs[:n].reshape(n, r1 - r0, B)
+        for r in range(r1 - r0):                                  # summed one by one: the bits do not depend on the chunking
+            gq += part[:, r]
+    return gq
 
 
 def _restrict(world, x: torch.Tensor, what: str, block: str):
@@ -182,6 +262,142 @@ class MassMatrixLayer(torch.autograd.Function):
         return None, _give(world, ds, ctx.state_device)
 
 
+class ForwardDynamicsLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, world, state, tau, flags):
+        _join_if_deferred(world)
+        n = world.n
+        x, ctx.ref_s, ctx.width_s = _restrict(world, state.detach(), "forward_dynamics", "state")
+        lead = tuple(x.shape[:-1])
+        s_soa = world.to_soa(world._prep(x.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+        t_soa = None
+        if tau is not None:
+            t, ctx.ref_t, ctx.width_t = _restrict(world, tau.detach(), "forward_dynamics", "tau")
+            if tuple(t.shape[:-1]) != lead:
+                raise ValueError(f"forward_dynamics: tau has leading shape {tuple(t.shape[:-1])}, state {lead}")
+            t_soa = world.to_soa(world._prep(t.reshape(-1, n), n, "dyn_accel"))
+            ctx.tau_device = tau.device
+        acc = forward_dynamics_soa(world, s_soa, t_soa, flags)
+        out = world.from_soa(acc).reshape(lead + (n,))
+        if ctx.ref_s:                                             # zero acceleration of the frozen coordinates
+            out = _expand(world, out, lead, ctx.width_s // 2, "accel")
+        ctx.world, ctx.s_soa, ctx.t_soa, ctx.flags, ctx.lead, ctx.state_device = world, s_soa, t_soa, flags, lead, state.device
+        return _give(world, out, state.device)
+
+    @staticmethod
+    def backward(ctx, grad_accel):
+        world, n, lead = ctx.world, ctx.world.n, ctx.lead
+        g = grad_accel.detach().to(device=world.device, dtype=torch.float64)
+        if ctx.ref_s:
+            g = g.index_select(-1, world.ref_layout._idx(world.device, "mobile"))
+        want_s = ctx.needs_input_grad[1]
+        want_t = ctx.t_soa is not None and ctx.needs_input_grad[2]
+        gs, gt = forward_dynamics_vjp_soa(world, ctx.s_soa, ctx.t_soa, world.to_soa(g.reshape(-1, n)), ctx.flags, want_s, want_t)
+        ds = dt = None
+        if want_s:
+            ds = world.from_soa(gs).reshape(lead + (2 * n,))
+            if ctx.ref_s:
+                ds = _expand(world, ds, lead, ctx.width_s, "state")
+            ds = _give(world, ds, ctx.state_device)
+        if want_t:
+            dt = world.from_soa(gt).reshape(lead + (n,))
+            if ctx.ref_t:
+                dt = _expand(world, dt, lead, ctx.width_t, "tau")
+            dt = _give(world, dt, ctx.tau_device)
+        return None, ds, dt, None
+
+
+def _state_grad_q(world, gq: torch.Tensor, ctx):
+    """[n, B] position cotangent -> the cotangent of `state` (the velocity block receives nothing)"""
+    n, lead = world.n, ctx.lead
+    ds = world.from_soa(torch.cat([gq, torch.zeros_like(gq)], 0)).reshape(lead + (2 * n,))
+    if ctx.ref_s:
+        ds = _expand(world, ds, lead, ctx.width_s, "state")
+    return _give(world, ds, ctx.state_device)
+
+
+class InvMassApplyLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, world, state, x):
+        _join_if_deferred(world)
+        n = world.n
+        s, ctx.ref_s, ctx.width_s = _restrict(world, state.detach(), "multiply_by_inv_mass_matrix", "state")
+        lead = tuple(s.shape[:-1])
+        ctx.matrix = x.dim() == state.dim() + 1                   # [..., n, R]; else [..., n]
+        xr = x.detach().transpose(-1, -2) if ctx.matrix else x.detach().unsqueeze(-2)      # [..., R, n]
+        xr, ctx.ref_x, ctx.width_x = _restrict(world, xr, "multiply_by_inv_mass_matrix", "x")
+        if tuple(xr.shape[:-2]) != lead:
+            raise ValueError(f"multiply_by_inv_mass_matrix: x has leading shape {tuple(xr.shape[:-2])}, state {lead}")
+        R = xr.shape[-2]
+        if R < 1:
+            raise ValueError("multiply_by_inv_mass_matrix: x has no right-hand side")
+        s_soa = world.to_soa(world._prep(s.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+        B = s_soa.shape[1]
+        X = world._prep(xr.reshape(-1, n), n, "dyn_rhs").reshape(B, R, n).permute(1, 2, 0).contiguous()    # [R, n, B]
+        Y = inv_mass_apply_soa(world, s_soa, X)
+        ctx.world, ctx.s_soa, ctx.Y, ctx.lead, ctx.R, ctx.state_device, ctx.x_device = world, s_soa, Y, lead, R, state.device, x.device
+        return _give(world, InvMassApplyLayer._shape(ctx, Y, ctx.ref_s), state.device)
+
+    @staticmethod
+    def _shape(ctx, Y, ref):
+        """[R, n, B] -> [..., n, R] or [..., n], in the reference's layout if asked"""
+        world, n, lead, R = ctx.world, ctx.world.n, ctx.lead, ctx.R
+        out = Y.permute(2, 0, 1).reshape(lead + (R, n))
+        if ref:
+            out = _expand(world, out, lead + (R,), world.ref_layout.n_ref, "x")
+        return out.transpose(-1, -2).contiguous() if ctx.matrix else out.squeeze(-2)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        world, n, R = ctx.world, ctx.world.n, ctx.R
+        g = grad_y.detach().to(device=world.device, dtype=torch.float64)
+        g = g.transpose(-1, -2) if ctx.matrix else g.unsqueeze(-2)                         # [..., R, n(_ref)]
+        if ctx.ref_s:
+            g = g.index_select(-1, world.ref_layout._idx(world.device, "mobile"))
+        B = ctx.s_soa.shape[1]
+        Lam = inv_mass_apply_soa(world, ctx.s_soa, g.reshape(B, R, n).permute(1, 2, 0).contiguous())
+        ds = _state_grad_q(world, _minv_grad_q(world, ctx.s_soa, ctx.Y, Lam), ctx) if ctx.needs_input_grad[1] else None
+        dx = _give(world, InvMassApplyLayer._shape(ctx, Lam, ctx.ref_x), ctx.x_device) if ctx.needs_input_grad[2] else None
+        return None, ds, dx
+
+
+class InvMassMatrixLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, world, state):
+        _join_if_deferred(world)
+        n = world.n
+        x, ctx.ref_s, ctx.width_s = _restrict(world, state.detach(), "inv_mass_matrix", "state")
+        lead = tuple(x.shape[:-1])
+        s_soa = world.to_soa(world._prep(x.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+        Mi = inv_mass_matrix_soa(world, s_soa)
+        out = world.from_soa(Mi).reshape(lead + (n, n))
+        if ctx.ref_s:                                             # zero rows and columns of the frozen coordinates
+            out = _expand_square(world, out, lead)
+        ctx.world, ctx.s_soa, ctx.Mi, ctx.lead, ctx.state_device = world, s_soa, Mi, lead, state.device
+        return _give(world, out, state.device)
+
+    @staticmethod
+    def backward(ctx, grad_Mi):
+        """Lambda = M^-1 G; grad_q = -sum_j (d (M y_j) / dq)^T lambda_j, y_j / lambda_j = column j of M^-1 / of Lambda."""
+        world, n = ctx.world, ctx.world.n
+        G = grad_Mi.detach().to(device=world.device, dtype=torch.float64)
+        if ctx.ref_s:
+            ix = world.ref_layout._idx(world.device, "mobile")
+            G = G.index_select(-1, ix).index_select(-2, ix)
+        B = ctx.s_soa.shape[1]
+        Lam = inv_mass_apply_soa(world, ctx.s_soa, G.reshape(B, n, n).permute(2, 1, 0).contiguous())    # [j, i, b]
+        Y = ctx.Mi.reshape(n, n, B)                                # [j][i][b] = Minv[i][j]: the matrix is symmetric bit for bit
+        return None, _state_grad_q(world, _minv_grad_q(world, ctx.s_soa, Y, Lam), ctx)
+
+
+def _expand_square(world, M: torch.Tensor, lead) -> torch.Tensor:
+    """[..., n, n] over the mobile coordinates -> [..., n_ref, n_ref] with zero rows and columns for the frozen ones"""
+    lay = world.ref_layout
+    ix = lay._idx(world.device, "mobile")
+    rows = torch.zeros(lead + (world.n, lay.n_ref), dtype=torch.float64, device=world.device).index_copy(-1, ix, M)
+    return torch.zeros(lead + (lay.n_ref, lay.n_ref), dtype=torch.float64, device=world.device).index_copy(-2, ix, rows)
+
+
 def inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, joint_forces: bool = False) -> torch.Tensor:
     """tau = M(q) a + C(q, v) of `state` = [q; v] ([..., 2n]) and `accel` ([..., n]) -> [..., n]; differentiable in both (exactly).
     joint_forces: + damping v + spring (q - rest + dt v), so that tau applied in timestep() reproduces accel."""
@@ -196,6 +412,29 @@ def coriolis_and_gravity(world, state: torch.Tensor) -> torch.Tensor:
 def mass_matrix(world, state: torch.Tensor) -> torch.Tensor:
     """M(q) of `state` ([..., 2n] -> [..., n, n]; only the positions are read), exactly symmetric; differentiable in the positions."""
     return MassMatrixLayer.apply(world, state)
+
+
+def forward_dynamics(world, state: torch.Tensor, tau: torch.Tensor, joint_forces: bool = False) -> torch.Tensor:
+    """a = M(q)^-1 (tau - C(q, v)) of `state` = [q; v] ([..., 2n]) and `tau` ([..., n]; None: 0) -> [..., n], by the articulated-body
+    algorithm; differentiable in both (exactly).  joint_forces: the right-hand side also carries - damping v - spring (q - rest + dt v) as
+    the step has it, so that a = (v' - v) / dt of a contact-free timestep() and forward_dynamics inverts inverse_dynamics under the same
+    switch.  With a `state` in the reference's layout (immobile skeletons) the result is in that layout too: zero acceleration and zero
+    gradient for the frozen coordinates."""
+    return ForwardDynamicsLayer.apply(world, state, tau, ID_JOINT_FORCES if joint_forces else 0)
+
+
+def multiply_by_inv_mass_matrix(world, state: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """M(q)^-1 x of `state` ([..., 2n]; only the positions are read) and x = [..., n] or [..., n, R] (R right-hand sides per world: the
+    articulated inertias are built once) -> the shape of x.  M is never formed.  Differentiable in x and in the positions (the velocity
+    block receives nothing).  In the reference's layout the frozen coordinates get zeros in the result and in the gradients."""
+    return InvMassApplyLayer.apply(world, state, x)
+
+
+def inv_mass_matrix(world, state: torch.Tensor) -> torch.Tensor:
+    """M(q)^-1 of `state` ([..., 2n] -> [..., n, n]), exactly symmetric; differentiable in the positions.  In the reference's layout the
+    frozen coordinates have zero rows and columns (the reference's own matrix has the inverse of their blocks there, which a model that
+    welded them to the world cannot give)."""
+    return InvMassMatrixLayer.apply(world, state)
 
 
 def _current(world):
@@ -216,3 +455,9 @@ def world_coriolis_and_gravity(world) -> torch.Tensor:
     s = _current(world)
     c = world.from_soa(inverse_dynamics_soa(world, s, None, 0))
     return c[0] if getattr(world, "_one_d", False) else c
+
+
+def world_inv_mass_matrix(world) -> torch.Tensor:
+    s = _current(world)
+    Mi = world.from_soa(inv_mass_matrix_soa(world, s)).reshape(s.shape[1], world.n, world.n)
+    return Mi[0] if getattr(world, "_one_d", False) else Mi

@@ -366,6 +366,12 @@ class World:
         from .dynamics import world_mass_matrix
         return world_mass_matrix(self)
 
+    def getInvMassMatrix(self) -> torch.Tensor:
+        """World::getInvMassMatrix on the current state: [B, n, n] ([n, n] for a 1-D state), exactly symmetric, by the articulated-body
+        recursion (M itself is never formed); see getMassMatrix."""
+        from .dynamics import world_inv_mass_matrix
+        return world_inv_mass_matrix(self)
+
     def getCoriolisAndGravityForces(self) -> torch.Tensor:
         """World::getCoriolisAndGravityForces on the current state: [B, n] ([n] for a 1-D state); see getMassMatrix."""
         from .dynamics import world_coriolis_and_gravity

@@ -1,8 +1,12 @@
 """Developer tool: time the joint-space dynamics entry points next to the contact-free step, in one process on the same states.
     python tools/dynamics_bench.py [--reps 30] [--out FILE.json] [--models atlas20,atlas33] [--batches 4096,32768]
 Atlas-20 and Atlas-33 at B = 4096 and 32768: nbl_inverse_dynamics_forward, nbl_inverse_dynamics_backward, nbl_mass_matrix, the n x B
-reverse launch of mass_matrix's backward pass, and nbl_step_forward (no colliders, record kept).  HIP events around every call on
-preallocated buffers, 5 warm-up calls, the median of --reps; one JSON line per configuration."""
+reverse launch of mass_matrix's backward pass, nbl_step_forward (no colliders, record kept), then nbl_forward_dynamics_forward / _backward,
+nbl_inv_mass_matrix and nbl_inv_mass_apply (R = 1) with their ratios to the inverse-dynamics (RNEA) call, next to the dense route to the
+same results through the public functions: torch.linalg.solve(mass_matrix, tau - coriolis_and_gravity) and torch.linalg.inv(mass_matrix)
+(with forward_dynamics / inv_mass_matrix through the same public layer beside them, transposes included on both sides).  HIP events around
+every call on preallocated buffers, 5 warm-up calls, the median of --reps (the new rows also carry the 10th and 90th percentile); one
+JSON line per configuration."""
 import argparse
 import ctypes as C
 import json
@@ -15,10 +19,10 @@ import numpy as np
 import torch
 
 import nimblephysics_amd as na
-from nimblephysics_amd.dynamics import ID_NO_GRAVITY, ID_NO_VELOCITY, _workspace
+from nimblephysics_amd.dynamics import ID_NO_GRAVITY, ID_NO_VELOCITY, _fd_workspace, _workspace
 
 
-def median_ms(fn, reps, warmup=5):
+def times_ms(fn, reps, warmup=5):
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -28,7 +32,18 @@ def median_ms(fn, reps, warmup=5):
         e0.record(); fn(); e1.record()
         e1.synchronize()
         out.append(e0.elapsed_time(e1))
-    return float(np.median(out))
+    return out
+
+
+def median_ms(fn, reps, warmup=5):
+    return float(np.median(times_ms(fn, reps, warmup)))
+
+
+def spread(r, key, fn, reps):
+    """median into r[key + "_ms"], [p10, p90] into r[key + "_p10_p90_ms"]"""
+    t = times_ms(fn, reps)
+    r[key + "_ms"] = float(np.median(t))
+    r[key + "_p10_p90_ms"] = [float(np.percentile(t, 10)), float(np.percentile(t, 90))]
 
 
 def main():
@@ -68,9 +83,27 @@ def main():
             status = torch.empty(B, dtype=torch.int32, device=dev)
             r["step_forward_ms"] = median_ms(lambda: w.step_into(s, u, nxt, saved, status), args.reps)
             r["id_forward_over_step"] = r["inverse_dynamics_forward_ms"] / r["step_forward_ms"]
+            # forward dynamics and M^-1 (articulated-body recursion), as ratios to the RNEA call at the same B
+            acc, gt1, lam = torch.empty_like(a), torch.empty_like(a), torch.empty_like(a)
+            Mi = M                                                  # (same size; M is not needed any more)
+            fws = _fd_workspace(w, B)
+            spread(r, "forward_dynamics_forward", lambda: L.nbl_forward_dynamics_forward(h, B, p(s), p(a), 0, p(acc), p(fws), fws.numel(), st), args.reps)
+            spread(r, "forward_dynamics_backward", lambda: L.nbl_forward_dynamics_backward(h, B, p(s), p(a), 0, p(g), p(gs), p(gt1), 0, p(fws), fws.numel(), st), args.reps)
+            spread(r, "inv_mass_matrix", lambda: L.nbl_inv_mass_matrix(h, B, p(s), p(Mi), p(fws), fws.numel(), st), args.reps)
+            spread(r, "inv_mass_apply_r1", lambda: L.nbl_inv_mass_apply(h, B, 1, p(s), p(g), p(lam), p(fws), fws.numel(), st), args.reps)
+            for k in ("forward_dynamics_forward", "forward_dynamics_backward", "inv_mass_matrix", "inv_mass_apply_r1"):
+                r[k + "_over_rnea"] = r[k + "_ms"] / r["inverse_dynamics_forward_ms"]
+            # what the same results cost through the dense route of the public functions, and the tree route through the same layer
+            sb, tb = s.t().contiguous(), a.t().contiguous()
+            spread(r, "dense_solve_route", lambda: torch.linalg.solve(na.mass_matrix(w, sb), (tb - na.coriolis_and_gravity(w, sb)).unsqueeze(-1)), args.reps)
+            spread(r, "public_forward_dynamics", lambda: na.forward_dynamics(w, sb, tb), args.reps)
+            spread(r, "dense_inv_route", lambda: torch.linalg.inv(na.mass_matrix(w, sb)), args.reps)
+            spread(r, "public_inv_mass_matrix", lambda: na.inv_mass_matrix(w, sb), args.reps)
+            r["dense_solve_over_forward_dynamics"] = r["dense_solve_route_ms"] / r["public_forward_dynamics_ms"]
+            r["dense_inv_over_inv_mass_matrix"] = r["dense_inv_route_ms"] / r["public_inv_mass_matrix_ms"]
             print(json.dumps(r), flush=True)
             rows.append(r)
-            del w, ws
+            del w, ws, fws
             torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
