@@ -496,7 +496,10 @@ int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, c
  * state [2n][B] = [q; v], accel / tau / grad_* [n][B], M [n * n][B] (row-major n x n per world), device pointers, SoA like the step's.
  * B may be (T + 1) x worlds: a whole rollout in one launch.  workspace: device scratch of nbl_dynamics_workspace_bytes(m, B) bytes (one
  * size serves the three calls); calls that share a workspace must be ordered on one stream.  Stream-ordered, no synchronisation, no
- * atomics: bit-reproducible.  Not covered: external forces on bodies and Skeleton::getInverseDynamicsFromPredictions. */
+ * atomics: bit-reproducible.  External wrenches on bodies, Skeleton::getContactInverseDynamics, getMultipleContactInverseDynamics and what
+ * getInverseDynamicsFromPredictions needs are covered by the nbl_*_wrench_* calls and nbl_contact_inverse_dynamics further down.  Not
+ * covered: the ...NearCoP variant of the contact solve (createMultipleContactInverseDynamicsNearCoPProblem), the ...OverTime variant, and
+ * gradients through the contact solve. */
 #define NBL_ID_NO_VELOCITY 1  /* take v as 0 */
 #define NBL_ID_NO_GRAVITY 2   /* leave gravity out */
 #define NBL_ID_JOINT_FORCES 4 /* + damping v + spring (q - rest + dt v) per DOF: the terms nbl_step_forward puts on the right-hand side, so
@@ -543,6 +546,57 @@ int32_t nbl_inv_mass_apply(nbl_model* m, int64_t B, int32_t R, const double* sta
                            size_t workspace_bytes, void* stream);
 /* Minv [n * n][B] (row-major n x n per world) = M(q)^-1: one triangle is computed and mirrored, Minv[i][j] and Minv[j][i] are the same bits. */
 int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- wrenches on bodies in the dynamics calls, contact inverse dynamics (csrc/dynamics.hip) ---------------------------------------------------
+ * A WRENCH SET is an nbl_kin_map whose entries are all NBL_KIN_SPATIAL (any other kind: NBL_E_BADARG): entry e names the frame
+ * F_e = W_body T_offset, and rows 6 e .. 6 e + 5 of wrench [6 E][B] (SoA, device pointer) are [torque(3); force(3)] on it - expressed in
+ * F_e and acting at its origin (BodyNode::setExtWrench; the local Jacobian of Skeleton::getJacobian(body)), or, with NBL_WRENCH_WORLD, in
+ * world coordinates, acting at the origin of F_e.  The generalized force of a set is tau_ext = sum_e J_e^T W_e, and
+ *   nbl_inverse_dynamics_wrench_forward:  tau = M(q) a + C(q, v) - tau_ext        nbl_forward_dynamics_wrench_forward:  a = M(q)^-1 (tau + tau_ext - C(q, v))
+ * (plus the NBL_ID_JOINT_FORCES terms): inverse functions of each other under equal flags and wrenches.  The argument lists are those of
+ * the calls without wrenches with (k, wrench) added, and grad_wrench [6 E][B] in the reverse passes: grad_wrench = (accumulate: +=)
+ * -J grad_tau (inverse dynamics) / J lambda, lambda = M^-1 grad_accel (forward dynamics), in the coordinates the wrenches came in;
+ * grad_state is exact in both frames (with NBL_WRENCH_WORLD it includes how R_F^T turns with the ancestors' coordinates).  k NULL: a set
+ * with no entries (wrench, grad_wrench unused) - the results of the calls without wrenches, bit for bit; so are those of an all-zero
+ * wrench array.  An entry fixed in the world (body -1) moves nothing.  NBL_WRENCH_WORLD is a flag of these four calls only.
+ * workspace: nbl_wrench_workspace_bytes(m, k, B) bytes of device scratch (the forward-dynamics workspace plus 3 doubles per body and 12 per
+ * entry, per world; one size serves all six calls); calls that share a workspace must be ordered on one stream.  Errors as for the
+ * dynamics calls: NBL_E_BADARG (null handle / state / output / workspace, a null wrench array for a set with entries, B < 0, unknown
+ * flag bits, a map made for another model, a non-spatial entry), NBL_E_WORKSPACE; nothing is launched then.  B = 0 is a no-op.
+ * Stream-ordered, no synchronisation, no atomics, bit-reproducible and independent of B and of a world's place in the batch. */
+#define NBL_WRENCH_WORLD 8 /* wrenches in world coordinates, acting at the origin of their entry's frame */
+size_t nbl_wrench_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B);
+int32_t nbl_inverse_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                            const double* wrench, int32_t flags, double* tau, void* workspace, size_t workspace_bytes,
+                                            void* stream);
+int32_t nbl_inverse_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                             const double* wrench, int32_t flags, const double* grad_tau, double* grad_state, double* grad_accel,
+                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int32_t nbl_forward_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                            const double* wrench, int32_t flags, double* accel, void* workspace, size_t workspace_bytes,
+                                            void* stream);
+int32_t nbl_forward_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                             const double* wrench, int32_t flags, const double* grad_accel, double* grad_state, double* grad_tau,
+                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* Contact inverse dynamics (Skeleton::getContactInverseDynamics, getMultipleContactInverseDynamics; Skeleton.cpp:9705-9949): the wrenches
+ * wrench_out [6 E][B] on the entries' frames (local coordinates) under which the accelerations accel [n][B] need NO torque on the six
+ * coordinates of the free root joint above them, and the joint torques tau [n][B] = M a + C - J^T W that go with them (the root's six rows
+ * are set to 0).  With r = the root's rows of M a + C (flags: NBL_ID_*, as in nbl_inverse_dynamics_forward) and A = J[:, root]^T (6 x 6 E):
+ *   NBL_CID_SINGLE      E = 1:  W = A^-1 r                                              (getContactInverseDynamics)
+ *   NBL_CID_NEAREST     W = W0 + A^T (A A^T)^-1 (r - A W0), W0 = wrench_guess [6 E][B]: the solution nearest to the guesses, what the
+ *                       reference's complete orthogonal decomposition returns for a full-row-rank A
+ *   NBL_CID_MIN_TORQUE  W = B^-1 A^T (A B^-1 A^T)^-1 r, B = diag(1, 1, 1, 0.01, 0.01, 0.01) per body: the closed form of the reference's
+ *                       KKT system for an empty guess list (wrench_guess is not read)
+ * through the LDL^T factorisation of the 6 x 6 matrix A D A^T per world; a pivot that is not positive (a rank-deficient A) writes NaN to
+ * that world's outputs only.  Every entry must hang below ONE body whose joint is the free joint at the root of its tree: otherwise
+ * NBL_E_UNSUPPORTED (the reference prints an error and returns zeros).  NBL_WRENCH_WORLD is not accepted (NBL_E_BADARG): the reference's
+ * wrenches are local.  Other errors as above, plus NBL_E_BADARG for an unknown mode, NBL_CID_SINGLE with E != 1 and NBL_CID_NEAREST without
+ * guesses.  No gradients flow through the solve (the reference has none).  Not offered: the ...NearCoP and ...OverTime variants. */
+#define NBL_CID_SINGLE 0
+#define NBL_CID_NEAREST 1
+#define NBL_CID_MIN_TORQUE 2
+int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                     const double* wrench_guess, int32_t mode, int32_t flags, double* wrench_out, double* tau, void* workspace,
+                                     size_t workspace_bytes, void* stream);
 /* ---- batched inverse kinematics (csrc/ik.hip) --------------------------------------------------------------------------------------------
  * IKMapping::setPositions (dart/neural/IKMapping.cpp:86-119) for B independent worlds: find joint positions whose mapped rows (the rows
  * of nbl_kinematics_forward) meet `target`.  The kernel restates math::solveIK with ONE restart and math::refineIK

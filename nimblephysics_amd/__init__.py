@@ -10,7 +10,8 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "atlas", "box_stack", "make_transform", "load_urdf", "load_skel", "with_ground", "load_model", "loadWorld", "model_from_nimble_world", "WrtMassBodyNodeEntryType", "GraphedStep", "GraphedRollout", "neural", "forwardPass", "BackpropSnapshot",
            "LossGradient", "LossGradientHighLevelAPI", "NimbleAmdError", "IKMapping", "map_to_pos", "map_to_vel", "MapToPosLayer",
            "MapToVelLayer", "inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics",
-           "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "IKConfig"]
+           "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "IKConfig", "contact_inverse_dynamics",
+           "inverse_dynamics_from_predictions"]
 
 
 def __getattr__(name):
@@ -40,7 +41,8 @@ def __getattr__(name):
     if name in ("IKMapping", "map_to_pos", "map_to_vel", "MapToPosLayer", "MapToVelLayer", "solve_ik", "IKConfig"):
         from . import mapping as _m
         return getattr(_m, name)
-    if name in ("inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics", "multiply_by_inv_mass_matrix", "inv_mass_matrix"):
+    if name in ("inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics", "multiply_by_inv_mass_matrix", "inv_mass_matrix",
+                "contact_inverse_dynamics", "inverse_dynamics_from_predictions"):
         from . import dynamics as _d
         return getattr(_d, name)
     if name in ("timestep", "TimestepLayer", "rollout", "RolloutLayer"):

@@ -24,6 +24,8 @@ NBL_E_NOGPU = -5
 ID_NO_VELOCITY = 1   # NBL_ID_*: the flags of the inverse- and forward-dynamics calls
 ID_NO_GRAVITY = 2
 ID_JOINT_FORCES = 4
+WRENCH_WORLD = 8      # NBL_WRENCH_WORLD: only the nbl_*_wrench_* calls take it
+CID_SINGLE, CID_NEAREST, CID_MIN_TORQUE = 0, 1, 2   # NBL_CID_*
 
 ST_CONTACT = 0x1
 ST_LCP_STAGE0 = 0x2

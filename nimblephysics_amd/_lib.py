@@ -146,6 +146,16 @@ def lib():
     L.nbl_ik_workspace_bytes.restype = C.c_size_t
     L.nbl_ik_solve.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.nbl_ik_solve.restype = C.c_int32
+    L.nbl_wrench_workspace_bytes.argtypes = [vp, vp, C.c_int64]
+    L.nbl_wrench_workspace_bytes.restype = C.c_size_t
+    for f in ("nbl_inverse_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_forward"):
+        getattr(L, f).argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, vp, vp, C.c_size_t, vp]
+        getattr(L, f).restype = C.c_int32
+    for f in ("nbl_inverse_dynamics_wrench_backward", "nbl_forward_dynamics_wrench_backward"):
+        getattr(L, f).argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+        getattr(L, f).restype = C.c_int32
+    L.nbl_contact_inverse_dynamics.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_contact_inverse_dynamics.restype = C.c_int32
     _lib = L
     return L
 
@@ -162,6 +172,8 @@ EXPORTED_SYMBOLS = [
     "nbl_dynamics_workspace_bytes", "nbl_inverse_dynamics_forward", "nbl_inverse_dynamics_backward", "nbl_mass_matrix",
     "nbl_forward_dynamics_workspace_bytes", "nbl_forward_dynamics_forward", "nbl_forward_dynamics_backward", "nbl_inv_mass_apply", "nbl_inv_mass_matrix",
     "nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve",
+    "nbl_wrench_workspace_bytes", "nbl_inverse_dynamics_wrench_forward", "nbl_inverse_dynamics_wrench_backward",
+    "nbl_forward_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_backward", "nbl_contact_inverse_dynamics",
 ]
 
 

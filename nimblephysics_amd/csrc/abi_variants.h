@@ -87,6 +87,12 @@
 #define nbl_ik_default_config NBL_V(nbl_ik_default_config)
 #define nbl_ik_workspace_bytes NBL_V(nbl_ik_workspace_bytes)
 #define nbl_ik_solve NBL_V(nbl_ik_solve)
+#define nbl_wrench_workspace_bytes NBL_V(nbl_wrench_workspace_bytes)
+#define nbl_inverse_dynamics_wrench_forward NBL_V(nbl_inverse_dynamics_wrench_forward)
+#define nbl_inverse_dynamics_wrench_backward NBL_V(nbl_inverse_dynamics_wrench_backward)
+#define nbl_forward_dynamics_wrench_forward NBL_V(nbl_forward_dynamics_wrench_forward)
+#define nbl_forward_dynamics_wrench_backward NBL_V(nbl_forward_dynamics_wrench_backward)
+#define nbl_contact_inverse_dynamics NBL_V(nbl_contact_inverse_dynamics)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

@@ -1633,6 +1633,8 @@ struct nbl_kin_map {
   void* dBuf = nullptr;                  // [count] DevKinEntry, then the ancestor chains (int32 device bodies, root -> entry body)
   DevKinEntry* dEntries = nullptr;
   int32_t* dPath = nullptr;
+  std::vector<DevKinEntry> hEntries;     // host copies: what the wrench calls check before they launch
+  std::vector<int32_t> hPath;
 };
 
 int32_t nbl_kin_map_create(nbl_model* m, int32_t count, const int32_t* kind, const int32_t* body, const double* T_offset, nbl_kin_map** out) {
@@ -1685,6 +1687,8 @@ int32_t nbl_kin_map_create(nbl_model* m, int32_t count, const int32_t* kind, con
   }
   km->dEntries = (DevKinEntry*)km->dBuf;
   km->dPath = (int32_t*)((char*)km->dBuf + eb);
+  km->hEntries = he;
+  km->hPath = path;
   *out = km;
   return NBL_OK;
 }
@@ -1870,6 +1874,133 @@ int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double
   DeviceGuard guard(m->device);
   hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
                      (const DevBody*)m->dBodies, m->mdl, B, (int)m->n, state, (const double*)nullptr, Minv, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// ---- wrenches on body frames in the dynamics calls, contact inverse dynamics (csrc/dynamics.hip) -----------------------------------------
+// workspace: the forward-dynamics layout ([nb][FD_SLOTS][B] tree slots, accel [n][B], -lambda [n][B]), then the moments of world-frame
+// wrenches [nb][3][B] and the root-to-entry transforms of the contact solve [E][12][B]
+static size_t wrenchCount(const nbl_kin_map* k) { return k ? (size_t)k->count : 0; }
+size_t nbl_wrench_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) {
+  if (!m || B <= 0) return 0;
+  return sizeof(double) * ((size_t)m->nb * (FD_SLOTS + 3) + 2 * (size_t)m->n + 12 * wrenchCount(k)) * (size_t)B;
+}
+
+// the checks the wrench calls share; k NULL: a set with no entries
+static int32_t wrenchCheck(const nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const void* out, const double* wrench,
+                           int32_t flags, int32_t flagMask, const void* workspace, size_t workspace_bytes) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (k && (k->n != m->n || k->nb != m->nb || k->device != m->device)) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  if (k)
+    for (int e = 0; e < k->count; e++)
+      if (k->hEntries[e].kind != KIN_SPATIAL)
+        return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the wrench set is not NBL_KIN_SPATIAL: a wrench needs a whole frame");
+  if (flags & ~flagMask) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~flagMask) + " (NBL_ID_*, NBL_WRENCH_WORLD)");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (B == 0) return NBL_OK;
+  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
+  if (k && !wrench) return fail(NBL_E_BADARG, "null wrench array for a set of " + std::to_string(k->count) + " entries");
+  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  const size_t need = nbl_wrench_workspace_bytes(m, k, B);
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "wrench workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_wrench_workspace_bytes() = " + std::to_string(need));
+  return NBL_OK;
+}
+#define NBL_WRENCH_SET(k) (const DevKinEntry*)((k) ? (k)->dEntries : nullptr), (const int32_t*)((k) ? (k)->dPath : nullptr), (int)wrenchCount(k)
+
+int32_t nbl_inverse_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                            const double* wrench, int32_t flags, double* tau, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  const int32_t rc = wrenchCheck(m, k, B, state, tau, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
+  if (rc != NBL_OK || B == 0) return rc;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_inverse_dynamics_wrench, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, NBL_WRENCH_SET(k), wrench, tau,
+                     (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_inverse_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                             const double* wrench, int32_t flags, const double* grad_tau, double* grad_state, double* grad_accel,
+                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = wrenchCheck(m, k, B, state, grad_tau, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
+  if (rc != NBL_OK || B == 0) return rc;
+  if (!grad_state && !grad_accel && !grad_wrench) return NBL_OK;
+  DeviceGuard guard(m->device);
+  double* ws = (double*)workspace;
+  double* wx = ws + ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
+  hipLaunchKernelGGL(k_inverse_dynamics_wrench_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, NBL_WRENCH_SET(k), wrench, grad_tau,
+                     grad_state, grad_accel, grad_wrench, accumulate ? 1 : 0, ws, wx);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_forward_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                            const double* wrench, int32_t flags, double* accel, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  const int32_t rc = wrenchCheck(m, k, B, state, accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
+  if (rc != NBL_OK || B == 0) return rc;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_forward_dynamics_wrench, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, accel,
+                     (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_forward_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                             const double* wrench, int32_t flags, const double* grad_accel, double* grad_state, double* grad_tau,
+                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = wrenchCheck(m, k, B, state, grad_accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
+  if (rc != NBL_OK || B == 0) return rc;
+  if (!grad_state && !grad_tau && !grad_wrench) return NBL_OK;
+  DeviceGuard guard(m->device);
+  double* ws = (double*)workspace;
+  double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
+  double* neglam = accel + (size_t)m->n * (size_t)B;
+  double* wx = neglam + (size_t)m->n * (size_t)B;
+  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
+  hipLaunchKernelGGL(k_forward_dynamics_wrench_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
+                     (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, grad_accel, accel, neglam, grad_tau,
+                     accumulate ? 1 : 0, ws);
+  HIP_TRY(hipGetLastError());
+  if (grad_state || grad_wrench) {   // grad_state (+)= -(d ID / d [q; v])^T lambda, grad_wrench (+)= J lambda, at (q, v, a) with the same wrenches
+    hipLaunchKernelGGL(k_inverse_dynamics_wrench_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
+                       (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, (const double*)accel, NBL_WRENCH_SET(k), wrench, (const double*)neglam,
+                       grad_state, (double*)nullptr, grad_wrench, accumulate ? 1 : 0, ws, wx);
+    HIP_TRY(hipGetLastError());
+  }
+  return NBL_OK;
+}
+
+int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                     const double* wrench_guess, int32_t mode, int32_t flags, double* wrench_out, double* tau, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (!k) return fail(NBL_E_BADARG, "null kinematics map: contact inverse dynamics needs at least one contact body");
+  if (mode != NBL_CID_SINGLE && mode != NBL_CID_NEAREST && mode != NBL_CID_MIN_TORQUE)
+    return fail(NBL_E_BADARG, "mode must be NBL_CID_SINGLE, NBL_CID_NEAREST or NBL_CID_MIN_TORQUE (got " + std::to_string(mode) + ")");
+  // (wrench_out stands in for the wrench array of the shared check: it is as long)
+  const int32_t rc = wrenchCheck(m, k, B, state, tau, wrench_out, flags, DYN_FLAG_MASK, workspace, workspace_bytes);
+  if (rc != NBL_OK) return rc;
+  if (mode == NBL_CID_SINGLE && k->count != 1)
+    return fail(NBL_E_BADARG, "NBL_CID_SINGLE takes one contact body (the set has " + std::to_string(k->count) + ")");
+  if (cidRoot(m->hBodies.data(), k->hEntries.data(), k->hPath.data(), k->count) < 0)
+    return fail(NBL_E_UNSUPPORTED, "contact inverse dynamics needs every contact body below ONE free joint at the root of its tree "
+                                   "(Skeleton::getContactInverseDynamics returns zeros otherwise)");
+  if (B == 0) return NBL_OK;
+  if (mode == NBL_CID_NEAREST && !wrench_guess) return fail(NBL_E_BADARG, "NBL_CID_NEAREST needs wrench_guess");
+  if (!accel) return fail(NBL_E_BADARG, "null argument");
+  DeviceGuard guard(m->device);
+  double* ws = (double*)workspace;
+  double* xs = ws + ((size_t)m->nb * (FD_SLOTS + 3) + 2 * (size_t)m->n) * (size_t)B;
+  hipLaunchKernelGGL(k_contact_inverse_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, (int)mode, B, state, accel, NBL_WRENCH_SET(k),
+                     mode == NBL_CID_NEAREST ? wrench_guess : (const double*)nullptr, wrench_out, tau, ws, xs);
   HIP_TRY(hipGetLastError());
   return NBL_OK;
 }

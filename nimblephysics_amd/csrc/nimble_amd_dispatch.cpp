@@ -83,7 +83,18 @@
   void nbl_ik_default_config##S(nbl_ik_config*);                                                                                           \
   size_t nbl_ik_workspace_bytes##S(const void*, const void*, int64_t);                                                                     \
   int32_t nbl_ik_solve##S(void*, const void*, int64_t, const double*, const double*, const nbl_ik_config*, double*, double*, int32_t*,     \
-                          void*, size_t, void*);
+                          void*, size_t, void*);                                                                                             \
+  size_t nbl_wrench_workspace_bytes##S(const void*, const void*, int64_t);                                                                 \
+  int32_t nbl_inverse_dynamics_wrench_forward##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t,        \
+                                                 double*, void*, size_t, void*);                                                             \
+  int32_t nbl_inverse_dynamics_wrench_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t,       \
+                                                  const double*, double*, double*, double*, int32_t, void*, size_t, void*);                  \
+  int32_t nbl_forward_dynamics_wrench_forward##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t,        \
+                                                 double*, void*, size_t, void*);                                                             \
+  int32_t nbl_forward_dynamics_wrench_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t,       \
+                                                  const double*, double*, double*, double*, int32_t, void*, size_t, void*);                  \
+  int32_t nbl_contact_inverse_dynamics##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, int32_t,      \
+                                          double*, double*, void*, size_t, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -150,6 +161,12 @@ struct Variant {
   int32_t (*forward_dynamics_backward)(void*, int64_t, const double*, const double*, int32_t, const double*, double*, double*, int32_t, void*, size_t, void*);
   int32_t (*inv_mass_apply)(void*, int64_t, int32_t, const double*, const double*, double*, void*, size_t, void*);
   int32_t (*inv_mass_matrix)(void*, int64_t, const double*, double*, void*, size_t, void*);
+  size_t (*wrench_workspace_bytes)(const void*, const void*, int64_t);
+  int32_t (*inverse_dynamics_wrench_forward)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, double*, void*, size_t, void*);
+  int32_t (*inverse_dynamics_wrench_backward)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, const double*, double*, double*, double*, int32_t, void*, size_t, void*);
+  int32_t (*forward_dynamics_wrench_forward)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, double*, void*, size_t, void*);
+  int32_t (*forward_dynamics_wrench_backward)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, const double*, double*, double*, double*, int32_t, void*, size_t, void*);
+  int32_t (*contact_inverse_dynamics)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, int32_t, double*, double*, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -163,7 +180,9 @@ struct Variant {
    nbl_kinematics_forward##S, nbl_kinematics_backward##S, nbl_dynamics_workspace_bytes##S, nbl_inverse_dynamics_forward##S,                 \
    nbl_inverse_dynamics_backward##S, nbl_mass_matrix##S, nbl_ik_workspace_bytes##S, nbl_ik_solve##S,                        \
    nbl_forward_dynamics_workspace_bytes##S, nbl_forward_dynamics_forward##S, nbl_forward_dynamics_backward##S, nbl_inv_mass_apply##S,       \
-   nbl_inv_mass_matrix##S}
+   nbl_inv_mass_matrix##S, nbl_wrench_workspace_bytes##S, nbl_inverse_dynamics_wrench_forward##S,                                          \
+   nbl_inverse_dynamics_wrench_backward##S, nbl_forward_dynamics_wrench_forward##S, nbl_forward_dynamics_wrench_backward##S,                \
+   nbl_contact_inverse_dynamics##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -412,6 +431,46 @@ int32_t nbl_inv_mass_apply(nbl_model* m, int64_t B, int32_t R, const double* sta
 }
 int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream) {
   return NBL_FWD(m, inv_mass_matrix, B, state, Minv, workspace, workspace_bytes, stream);
+}
+
+// the wrench calls: a NULL map is a wrench set with no entries
+#define NBL_WRENCH_MAP_CHECK(m, k) \
+  if ((m) && (k) && (k)->v != (m)->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model")
+size_t nbl_wrench_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) {
+  return (m && (!k || k->v == m->v)) ? m->v->wrench_workspace_bytes(m->impl, k ? k->impl : nullptr, B) : 0;
+}
+int32_t nbl_inverse_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                            const double* wrench, int32_t flags, double* tau, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  NBL_WRENCH_MAP_CHECK(m, k);
+  return NBL_FWD(m, inverse_dynamics_wrench_forward, k ? k->impl : nullptr, B, state, accel, wrench, flags, tau, workspace, workspace_bytes, stream);
+}
+int32_t nbl_inverse_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                             const double* wrench, int32_t flags, const double* grad_tau, double* grad_state, double* grad_accel,
+                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  NBL_WRENCH_MAP_CHECK(m, k);
+  return NBL_FWD(m, inverse_dynamics_wrench_backward, k ? k->impl : nullptr, B, state, accel, wrench, flags, grad_tau, grad_state, grad_accel,
+                 grad_wrench, accumulate, workspace, workspace_bytes, stream);
+}
+int32_t nbl_forward_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                            const double* wrench, int32_t flags, double* accel, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  NBL_WRENCH_MAP_CHECK(m, k);
+  return NBL_FWD(m, forward_dynamics_wrench_forward, k ? k->impl : nullptr, B, state, tau, wrench, flags, accel, workspace, workspace_bytes, stream);
+}
+int32_t nbl_forward_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                             const double* wrench, int32_t flags, const double* grad_accel, double* grad_state, double* grad_tau,
+                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  NBL_WRENCH_MAP_CHECK(m, k);
+  return NBL_FWD(m, forward_dynamics_wrench_backward, k ? k->impl : nullptr, B, state, tau, wrench, flags, grad_accel, grad_state, grad_tau,
+                 grad_wrench, accumulate, workspace, workspace_bytes, stream);
+}
+int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
+                                     const double* wrench_guess, int32_t mode, int32_t flags, double* wrench_out, double* tau, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  NBL_WRENCH_MAP_CHECK(m, k);
+  return NBL_FWD(m, contact_inverse_dynamics, k ? k->impl : nullptr, B, state, accel, wrench_guess, mode, flags, wrench_out, tau, workspace,
+                 workspace_bytes, stream);
 }
 
 void nbl_ik_default_config(nbl_ik_config* c) { nbl_ik_default_config_c8(c); }   // (the same in every instantiation)

@@ -32,7 +32,13 @@ layout is restricted to the mobile coordinates as map_to_pos does; the outputs a
 frozen entries are zero.  The reference's own mass matrix has blocks for the immobile skeletons (their bodies keep their masses there),
 which this model - it welded them to the world - cannot give.
 
-Out of scope: external forces on bodies (add J^T f from the kinematics VJP to tau) and Skeleton::getInverseDynamicsFromPredictions.
+Wrenches on bodies: `inverse_dynamics` and `forward_dynamics` take `wrenches` ([..., 6 E]: [torque; force] per entry) on `bodies` (an
+IKMapping of spatial entries, or a list of body names / indices), expressed in each entry's frame and acting at its origin
+(BodyNode::setExtWrench) or, with `world_frame=True`, in world coordinates at that origin: tau = M a + C - sum_e J_e^T W_e and
+a = M^-1 (tau + sum_e J_e^T W_e - C), with exact gradients to the state, accel / tau AND the wrenches.  Built on them:
+`contact_inverse_dynamics` (Skeleton::getContactInverseDynamics / getMultipleContactInverseDynamics, Skeleton.cpp:9705-9949; no autograd,
+like the reference) and `inverse_dynamics_from_predictions` (Skeleton::getInverseDynamicsFromPredictions, Skeleton.cpp:9671-9697).
+Out of scope: the ...NearCoP and ...OverTime variants of the contact solve, and gradients through it.
 """
 from __future__ import annotations
 
@@ -43,6 +49,8 @@ from ._lib import check
 from .mapping import _join_if_deferred, _ptr
 
 ID_NO_VELOCITY, ID_NO_GRAVITY, ID_JOINT_FORCES = 1, 2, 4      # NBL_ID_* of include/nimble_amd.h
+WRENCH_WORLD = 8                                               # NBL_WRENCH_WORLD: the wrench calls only
+CID_SINGLE, CID_NEAREST, CID_MIN_TORQUE = 0, 1, 2              # NBL_CID_*
 # mass_matrix's backward pass launches the reverse kernel over (columns x B) worlds, and the workspace is 48 doubles per body and launched
 # world (Atlas-33, 34 bodies: 13 kB per world - 1.8 GB for all 33 columns of 4096 worlds).  Up to this many worlds go into ONE launch
 # (3.4 GB of workspace on Atlas-33); a larger batch - 32768 worlds, or a [B, T+1] rollout - is cut into launches of whole columns.
@@ -398,10 +406,175 @@ def _expand_square(world, M: torch.Tensor, lead) -> torch.Tensor:
     return torch.zeros(lead + (lay.n_ref, lay.n_ref), dtype=torch.float64, device=world.device).index_copy(-2, ix, rows)
 
 
-def inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, joint_forces: bool = False) -> torch.Tensor:
+# ---- wrenches on bodies -------------------------------------------------------------------------------------------------------------------
+def wrench_set(world, bodies):
+    """`bodies` -> the IKMapping of spatial entries the wrench calls take: an IKMapping is checked and passed on, a list of body names /
+    indices (of world.description.bodies) becomes one spatial entry each, in that order."""
+    from .mapping import KIN_SPATIAL, IKMapping
+    if isinstance(bodies, IKMapping):
+        if any(k != KIN_SPATIAL for k, _, _, _ in bodies._entries):
+            raise ValueError("wrenches need spatial entries (IKMapping.addSpatialBodyNode): a wrench acts on a whole frame")
+        return bodies
+    if bodies is None:
+        raise ValueError("wrenches need `bodies`: an IKMapping of spatial entries, or a list of body names / indices")
+    if isinstance(bodies, (str, int)):
+        bodies = [bodies]
+    m = IKMapping(world)
+    for b in bodies:
+        m.addSpatialBodyNode(b)
+    return m
+
+
+def _wr_workspace(world, km, B: int):
+    """The scratch of the wrench calls and of the contact solve, kept like _workspace."""
+    need = world._L.nbl_wrench_workspace_bytes(world._h, km, B)
+    ws = getattr(world, "_wrench_ws", None)
+    if ws is None or ws.numel() < need or ws.device != world.device:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=world.device)
+        world._wrench_ws = ws
+    return ws
+
+
+def _km(world, mapping):
+    """the device map of `mapping`, None (a set without entries) when it has none"""
+    return mapping._device_map(world) if mapping is not None and mapping._entries else None
+
+
+# raw SoA calls: state [2n][B], accel / tau [n][B], wrench [6 E][B]
+def inverse_dynamics_wrench_soa(world, mapping, s_soa, a_soa, w_soa, flags: int = 0) -> torch.Tensor:
+    B = s_soa.shape[1]
+    tau = torch.empty((world.n, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        km = _km(world, mapping)
+        ws = _wr_workspace(world, km, B)
+        check(world._L.nbl_inverse_dynamics_wrench_forward(world._h, km, B, _ptr(s_soa), _ptr(a_soa), _ptr(w_soa), flags, _ptr(tau), _ptr(ws),
+                                                           ws.numel(), world._stream()), "nbl_inverse_dynamics_wrench_forward")
+    return tau
+
+
+def forward_dynamics_wrench_soa(world, mapping, s_soa, t_soa, w_soa, flags: int = 0) -> torch.Tensor:
+    B = s_soa.shape[1]
+    acc = torch.empty((world.n, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        km = _km(world, mapping)
+        ws = _wr_workspace(world, km, B)
+        check(world._L.nbl_forward_dynamics_wrench_forward(world._h, km, B, _ptr(s_soa), _ptr(t_soa), _ptr(w_soa), flags, _ptr(acc), _ptr(ws),
+                                                           ws.numel(), world._stream()), "nbl_forward_dynamics_wrench_forward")
+    return acc
+
+
+def _wrench_vjp_soa(world, fn: str, mapping, s_soa, x_soa, w_soa, g_soa, flags, want_state, want_x, want_w):
+    """(grad_state [2n][B], grad of accel / tau [n][B], grad_wrench [6 E][B]) of one of the two reverse calls; None where not wanted"""
+    B, E6 = s_soa.shape[1], w_soa.shape[0]
+    dev = world.device
+    gs = torch.empty((2 * world.n, B), dtype=torch.float64, device=dev) if want_state else None
+    gx = torch.empty((world.n, B), dtype=torch.float64, device=dev) if want_x else None
+    gw = torch.empty((E6, B), dtype=torch.float64, device=dev) if want_w else None
+    if B > 0:
+        km = _km(world, mapping)
+        ws = _wr_workspace(world, km, B)
+        check(getattr(world._L, fn)(world._h, km, B, _ptr(s_soa), _ptr(x_soa), _ptr(w_soa), flags, _ptr(g_soa), _ptr(gs), _ptr(gx),
+                                    _ptr(gw) if E6 else None, 0, _ptr(ws), ws.numel(), world._stream()), fn)
+    return gs, gx, gw
+
+
+def contact_inverse_dynamics_soa(world, mapping, s_soa, a_soa, g_soa, mode: int, flags: int = ID_JOINT_FORCES):
+    """(wrenches [6 E][B], tau [n][B])"""
+    B, E6 = s_soa.shape[1], 6 * len(mapping._entries)
+    W = torch.empty((E6, B), dtype=torch.float64, device=world.device)
+    tau = torch.empty((world.n, B), dtype=torch.float64, device=world.device)
+    km = _km(world, mapping)
+    ws = _wr_workspace(world, km, max(B, 1))
+    check(world._L.nbl_contact_inverse_dynamics(world._h, km, B, _ptr(s_soa), _ptr(a_soa), _ptr(g_soa), mode, flags, _ptr(W), _ptr(tau), _ptr(ws),
+                                                ws.numel(), world._stream()), "nbl_contact_inverse_dynamics")
+    return W, tau
+
+
+def _wrench_inputs(world, what, mapping, wrenches, lead):
+    E6 = 6 * len(mapping._entries)
+    if wrenches.dim() == 0 or wrenches.shape[-1] != E6 or tuple(wrenches.shape[:-1]) != lead:
+        raise ValueError(f"{what}: wrenches have shape {tuple(wrenches.shape)}; expected {lead + (E6,)} ([torque; force] per entry)")
+    if E6 == 0:                                                   # a set without entries: nothing to upload
+        worlds = 1
+        for d in lead:
+            worlds *= d
+        return torch.empty((0, worlds), dtype=torch.float64, device=world.device)
+    return world.to_soa(world._prep(wrenches.detach().reshape(-1, E6), E6, "dyn_wrench"))
+
+
+class _WrenchLayer(torch.autograd.Function):
+    """inverse (FD = False) or forward (FD = True) dynamics with wrenches; x = accel or tau"""
+
+    @staticmethod
+    def forward(ctx, world, state, x, wrenches, mapping, flags, fd):
+        _join_if_deferred(world)
+        n = world.n
+        what = "forward_dynamics" if fd else "inverse_dynamics"
+        s, ctx.ref_s, ctx.width_s = _restrict(world, state.detach(), what, "state")
+        lead = tuple(s.shape[:-1])
+        s_soa = world.to_soa(world._prep(s.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+        x_soa = None
+        if x is not None:
+            xr, ctx.ref_x, ctx.width_x = _restrict(world, x.detach(), what, "tau" if fd else "accel")
+            if tuple(xr.shape[:-1]) != lead:
+                raise ValueError(f"{what}: {'tau' if fd else 'accel'} has leading shape {tuple(xr.shape[:-1])}, state {lead}")
+            x_soa = world.to_soa(world._prep(xr.reshape(-1, n), n, "dyn_accel"))
+            ctx.x_device = x.device
+        w_soa = _wrench_inputs(world, what, mapping, wrenches, lead)
+        out = (forward_dynamics_wrench_soa if fd else inverse_dynamics_wrench_soa)(world, mapping, s_soa, x_soa, w_soa, flags)
+        out = world.from_soa(out).reshape(lead + (n,))
+        if fd and ctx.ref_s:                                      # zero acceleration of the frozen coordinates
+            out = _expand(world, out, lead, ctx.width_s // 2, "accel")
+        ctx.world, ctx.mapping, ctx.s_soa, ctx.x_soa, ctx.w_soa, ctx.flags, ctx.fd, ctx.lead = world, mapping, s_soa, x_soa, w_soa, flags, fd, lead
+        ctx.state_device, ctx.w_device = state.device, wrenches.device
+        return _give(world, out, state.device)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        world, n, lead, fd = ctx.world, ctx.world.n, ctx.lead, ctx.fd
+        g = grad_out.detach().to(device=world.device, dtype=torch.float64)
+        if fd and ctx.ref_s:
+            g = g.index_select(-1, world.ref_layout._idx(world.device, "mobile"))
+        want_s = ctx.needs_input_grad[1]
+        want_x = ctx.x_soa is not None and ctx.needs_input_grad[2]
+        want_w = ctx.needs_input_grad[3] and ctx.w_soa.shape[0] > 0
+        fn = "nbl_forward_dynamics_wrench_backward" if fd else "nbl_inverse_dynamics_wrench_backward"
+        gs, gx, gw = _wrench_vjp_soa(world, fn, ctx.mapping, ctx.s_soa, ctx.x_soa, ctx.w_soa, world.to_soa(g.reshape(-1, n)), ctx.flags,
+                                     want_s, want_x, want_w)
+        ds = dx = dw = None
+        if want_s:
+            ds = world.from_soa(gs).reshape(lead + (2 * n,))
+            if ctx.ref_s:
+                ds = _expand(world, ds, lead, ctx.width_s, "state")
+            ds = _give(world, ds, ctx.state_device)
+        if want_x:
+            dx = world.from_soa(gx).reshape(lead + (n,))
+            if ctx.ref_x:
+                dx = _expand(world, dx, lead, ctx.width_x, "accel")
+            dx = _give(world, dx, ctx.x_device)
+        if want_w:
+            dw = _give(world, world.from_soa(gw).reshape(lead + (gw.shape[0],)), ctx.w_device)
+        elif ctx.needs_input_grad[3]:
+            dw = torch.zeros(lead + (0,), dtype=torch.float64, device=ctx.w_device)
+        return None, ds, dx, dw, None, None, None
+
+
+def _wrench_flags(joint_forces: bool, world_frame: bool) -> int:
+    return (ID_JOINT_FORCES if joint_forces else 0) | (WRENCH_WORLD if world_frame else 0)
+
+
+def inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, joint_forces: bool = False, wrenches=None, bodies=None,
+                     world_frame: bool = False) -> torch.Tensor:
     """tau = M(q) a + C(q, v) of `state` = [q; v] ([..., 2n]) and `accel` ([..., n]) -> [..., n]; differentiable in both (exactly).
-    joint_forces: + damping v + spring (q - rest + dt v), so that tau applied in timestep() reproduces accel."""
-    return InverseDynamicsLayer.apply(world, state, accel, ID_JOINT_FORCES if joint_forces else 0)
+    joint_forces: + damping v + spring (q - rest + dt v), so that tau applied in timestep() reproduces accel.
+    wrenches ([..., 6 E], [torque; force] per entry of `bodies`: an IKMapping of spatial entries, or body names / indices): tau also carries
+    - sum_e J_e^T W_e, the wrenches expressed in their entry's frame and acting at its origin (BodyNode::setExtWrench), or with
+    world_frame in world coordinates at that origin; differentiable in the wrenches too.  Without `wrenches` the call is what it was."""
+    if wrenches is None:
+        if bodies is not None or world_frame:
+            raise ValueError("inverse_dynamics: `bodies` / `world_frame` describe `wrenches`, which were not given")
+        return InverseDynamicsLayer.apply(world, state, accel, ID_JOINT_FORCES if joint_forces else 0)
+    return _WrenchLayer.apply(world, state, accel, wrenches, wrench_set(world, bodies), _wrench_flags(joint_forces, world_frame), False)
 
 
 def coriolis_and_gravity(world, state: torch.Tensor) -> torch.Tensor:
@@ -414,13 +587,106 @@ def mass_matrix(world, state: torch.Tensor) -> torch.Tensor:
     return MassMatrixLayer.apply(world, state)
 
 
-def forward_dynamics(world, state: torch.Tensor, tau: torch.Tensor, joint_forces: bool = False) -> torch.Tensor:
+def forward_dynamics(world, state: torch.Tensor, tau: torch.Tensor, joint_forces: bool = False, wrenches=None, bodies=None,
+                     world_frame: bool = False) -> torch.Tensor:
     """a = M(q)^-1 (tau - C(q, v)) of `state` = [q; v] ([..., 2n]) and `tau` ([..., n]; None: 0) -> [..., n], by the articulated-body
     algorithm; differentiable in both (exactly).  joint_forces: the right-hand side also carries - damping v - spring (q - rest + dt v) as
     the step has it, so that a = (v' - v) / dt of a contact-free timestep() and forward_dynamics inverts inverse_dynamics under the same
     switch.  With a `state` in the reference's layout (immobile skeletons) the result is in that layout too: zero acceleration and zero
-    gradient for the frozen coordinates."""
-    return ForwardDynamicsLayer.apply(world, state, tau, ID_JOINT_FORCES if joint_forces else 0)
+    gradient for the frozen coordinates.
+    wrenches / bodies / world_frame as in inverse_dynamics: a = M^-1 (tau + sum_e J_e^T W_e - C), its inverse function under equal
+    switches and wrenches; differentiable in the wrenches too.  Without `wrenches` the call is what it was."""
+    if wrenches is None:
+        if bodies is not None or world_frame:
+            raise ValueError("forward_dynamics: `bodies` / `world_frame` describe `wrenches`, which were not given")
+        return ForwardDynamicsLayer.apply(world, state, tau, ID_JOINT_FORCES if joint_forces else 0)
+    return _WrenchLayer.apply(world, state, tau, wrenches, wrench_set(world, bodies), _wrench_flags(joint_forces, world_frame), True)
+
+
+def contact_inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, bodies, wrench_guesses=None, min_torque: bool = False):
+    """Skeleton::getContactInverseDynamics / getMultipleContactInverseDynamics (Skeleton.cpp:9705-9949) for batches: the wrenches on the
+    contact `bodies` (local coordinates, [..., E, 6]) under which `accel` needs no torque on the six coordinates of the free root joint,
+    and the joint torques ([..., n], root rows 0) that go with them - with the damping and spring forces, like the reference.
+    One body and no guesses: getContactInverseDynamics.  Several bodies: with `wrench_guesses` ([..., E, 6] or [..., 6 E]) the solution
+    nearest to them; with none (or an empty list, or min_torque) the reference's min-torque solution.  Every body must hang below one
+    free root joint.  No autograd (the reference has none); a world whose 6 x 6 system is singular gets NaN."""
+    _join_if_deferred(world)
+    n = world.n
+    mapping = wrench_set(world, bodies)
+    E = len(mapping._entries)
+    if E < 1:
+        raise ValueError("contact_inverse_dynamics: no contact body")
+    s, _, _ = _restrict(world, state.detach(), "contact_inverse_dynamics", "state")
+    lead = tuple(s.shape[:-1])
+    a, _, _ = _restrict(world, accel.detach(), "contact_inverse_dynamics", "accel")
+    if tuple(a.shape[:-1]) != lead:
+        raise ValueError(f"contact_inverse_dynamics: accel has leading shape {tuple(a.shape[:-1])}, state {lead}")
+    s_soa = world.to_soa(world._prep(s.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+    a_soa = world.to_soa(world._prep(a.reshape(-1, n), n, "dyn_accel"))
+    g_soa = None
+    have = wrench_guesses is not None and not (isinstance(wrench_guesses, (list, tuple)) and len(wrench_guesses) == 0)
+    if have and not min_torque:
+        g = wrench_guesses if torch.is_tensor(wrench_guesses) else torch.stack([torch.as_tensor(x, dtype=torch.float64) for x in wrench_guesses], -2)
+        g = g.detach().reshape(tuple(g.shape[:-2]) + (6 * E,)) if g.shape[-1] == 6 and g.dim() == len(lead) + 2 else g.detach()
+        if tuple(g.shape) != lead + (6 * E,):
+            raise ValueError(f"contact_inverse_dynamics: wrench_guesses have shape {tuple(g.shape)}; expected {lead + (E, 6)}")
+        g_soa = world.to_soa(world._prep(g.reshape(-1, 6 * E), 6 * E, "dyn_wrench"))
+        mode = CID_NEAREST
+    else:
+        mode = CID_SINGLE if (E == 1 and not min_torque) else CID_MIN_TORQUE
+    W, tau = contact_inverse_dynamics_soa(world, mapping, s_soa, a_soa, g_soa, mode)
+    W = world.from_soa(W).reshape(lead + (E, 6))
+    tau = world.from_soa(tau).reshape(lead + (n,))
+    if state.device.type == "cpu":
+        return world._to_host(W, tau)
+    return W.to(state.device), tau.to(state.device)
+
+
+def _rotvec_matrix(r: torch.Tensor) -> torch.Tensor:
+    """exp([r]x) of rotation vectors [..., 3] -> [..., 3, 3] (Rodrigues), differentiable"""
+    th2 = (r * r).sum(-1, keepdim=True)
+    th = torch.sqrt(th2.clamp_min(1e-30))
+    small = th2 < 1e-12
+    A = torch.where(small, 1.0 - th2 / 6.0, torch.sin(th) / th)[..., None]
+    Bc = torch.where(small, 0.5 - th2 / 24.0, (1.0 - torch.cos(th)) / th2.clamp_min(1e-30))[..., None]
+    z = torch.zeros_like(r[..., 0])
+    K = torch.stack([torch.stack([z, -r[..., 2], r[..., 1]], -1), torch.stack([r[..., 2], z, -r[..., 0]], -1),
+                     torch.stack([-r[..., 1], r[..., 0], z], -1)], -2)
+    return torch.eye(3, dtype=r.dtype, device=r.device) + A * K + Bc * (K @ K)
+
+
+def inverse_dynamics_from_predictions(world, state: torch.Tensor, accel: torch.Tensor, bodies, root_frame_wrenches: torch.Tensor,
+                                      root_residuals=None) -> torch.Tensor:
+    """Skeleton::getInverseDynamicsFromPredictions (Skeleton.cpp:9671-9697): the joint torques ([..., n]) for `accel` given predicted
+    wrenches on the contact `bodies` expressed in the ROOT body's frame ([..., E, 6] or [..., 6 E]) and, optionally, a residual wrench on
+    the root body in its own frame ([..., 6]).  The reference's dAdInvT(T_wb^-1, dAdInvT(T_wr, W)) is the wrench in world coordinates
+    taken to each body's origin - [R_wr t + (p_wr - p_wb) x R_wr f; R_wr f] - which inverse_dynamics takes as it is (world_frame); the
+    residual is one more wrench on the root body, local there.  The root is the body of `bodies[0]`'s tree root.  With the damping and
+    spring forces, like the reference; differentiable like inverse_dynamics."""
+    from .mapping import map_to_pos
+    contact = wrench_set(world, bodies)
+    E = len(contact._entries)
+    md = world.description
+    if E < 1:
+        raise ValueError("inverse_dynamics_from_predictions: no contact body")
+    r = contact._entries[0][1]
+    while md.bodies[r].parent >= 0:
+        r = md.bodies[r].parent
+    allm = wrench_set(world, [i for _, i, _, _ in contact._entries] + [r])         # the contact bodies, then the root
+    W = root_frame_wrenches.reshape(tuple(root_frame_wrenches.shape[:-2]) + (6 * E,)) if root_frame_wrenches.shape[-1] == 6 and \
+        root_frame_wrenches.dim() == state.dim() + 1 else root_frame_wrenches
+    pos = map_to_pos(world, allm, state).to(W.device)                      # [..., 6 (E + 1)]: logMap(R), p per entry
+    Rr = _rotvec_matrix(pos[..., 6 * E:6 * E + 3])
+    pr = pos[..., 6 * E + 3:6 * E + 6]
+    parts = []
+    for e in range(E):
+        t = (Rr @ W[..., 6 * e:6 * e + 3, None])[..., 0]
+        f = (Rr @ W[..., 6 * e + 3:6 * e + 6, None])[..., 0]
+        parts += [t + torch.linalg.cross(pr - pos[..., 6 * e + 3:6 * e + 6], f), f]
+    if root_residuals is not None:                                                  # local on the root = world coordinates turned by R_wr
+        parts += [(Rr @ root_residuals[..., 0:3, None])[..., 0], (Rr @ root_residuals[..., 3:6, None])[..., 0]]
+        return inverse_dynamics(world, state, accel, True, torch.cat(parts, -1), allm, True)
+    return inverse_dynamics(world, state, accel, True, torch.cat(parts, -1), contact, True)
 
 
 def multiply_by_inv_mass_matrix(world, state: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -455,6 +721,49 @@ def world_coriolis_and_gravity(world) -> torch.Tensor:
     s = _current(world)
     c = world.from_soa(inverse_dynamics_soa(world, s, None, 0))
     return c[0] if getattr(world, "_one_d", False) else c
+
+
+def _world_vec(world, x, what):
+    """a per-world vector given like the state was ([n] for a 1-D state, else [B, n]; the reference's layout allowed) -> [n][B]"""
+    x = torch.as_tensor(x, dtype=torch.float64)
+    x, _, _ = _restrict(world, x, what, "accel")
+    return world.to_soa(world._prep(x.reshape(-1, world.n), world.n, "dyn_accel"))
+
+
+def _world_torques(world, tau_soa):
+    """[n][B] -> [B, n] ([n] for a 1-D state); in the reference's layout the frozen coordinates get zeros"""
+    t = world.from_soa(tau_soa)
+    if world.ref_layout is not None:
+        t = _expand(world, t, (t.shape[0],), world.ref_layout.n_ref, "accel")
+    return t[0] if getattr(world, "_one_d", False) else t
+
+
+def world_contact_inverse_dynamics(world, accel, bodies, wrench_guesses=None, multiple=False):
+    s = _current(world)
+    mapping = wrench_set(world, bodies)
+    E, B = len(mapping._entries), s.shape[1]
+    a_soa = _world_vec(world, accel, "getContactInverseDynamics")
+    g_soa, mode = None, CID_SINGLE if not multiple else CID_MIN_TORQUE
+    if multiple and wrench_guesses is not None and len(wrench_guesses) > 0:
+        g = wrench_guesses if torch.is_tensor(wrench_guesses) else torch.stack([torch.as_tensor(x, dtype=torch.float64) for x in wrench_guesses], -2)
+        g_soa = world.to_soa(world._prep(g.reshape(-1, 6 * E), 6 * E, "dyn_wrench"))
+        mode = CID_NEAREST
+    W, tau = contact_inverse_dynamics_soa(world, mapping, s, a_soa, g_soa, mode)
+    W = world.from_soa(W).reshape(B, E, 6)
+    return (W[0] if getattr(world, "_one_d", False) else W), _world_torques(world, tau)
+
+
+def world_inverse_dynamics_from_predictions(world, accel, bodies, root_frame_wrenches, root_residuals=None):
+    s = _current(world)
+    state = world.from_soa(s)
+    one = getattr(world, "_one_d", False)
+    a = world.from_soa(_world_vec(world, accel, "getInverseDynamicsFromPredictions"))
+    W = torch.as_tensor(root_frame_wrenches, dtype=torch.float64).to(world.device).reshape(state.shape[0], -1)
+    res = None if root_residuals is None else torch.as_tensor(root_residuals, dtype=torch.float64).to(world.device).reshape(state.shape[0], 6)
+    tau = inverse_dynamics_from_predictions(world, state, a, bodies, W, res)
+    if world.ref_layout is not None:
+        tau = _expand(world, tau, (tau.shape[0],), world.ref_layout.n_ref, "accel")
+    return tau[0] if one else tau
 
 
 def world_inv_mass_matrix(world) -> torch.Tensor:

@@ -377,6 +377,25 @@ class World:
         from .dynamics import world_coriolis_and_gravity
         return world_coriolis_and_gravity(self)
 
+    def getContactInverseDynamics(self, accelerations, body):
+        """Skeleton::getContactInverseDynamics on the current state: (contact wrench [B, 6], joint torques [B, n]; [6], [n] for a 1-D
+        state) for the accelerations [B, n] ([n]); `body` is a body name or index.  With immobile skeletons the frozen coordinates get zeros."""
+        from .dynamics import world_contact_inverse_dynamics
+        W, tau = world_contact_inverse_dynamics(self, accelerations, [body], None, multiple=False)
+        return W[..., 0, :], tau
+
+    def getMultipleContactInverseDynamics(self, accelerations, bodies, wrench_guesses=None):
+        """Skeleton::getMultipleContactInverseDynamics on the current state: (contact wrenches [B, E, 6], joint torques [B, n]); with
+        `wrench_guesses` ([B, E, 6]) the solution nearest to them, with none (or an empty list) the min-torque one, as in the reference."""
+        from .dynamics import world_contact_inverse_dynamics
+        return world_contact_inverse_dynamics(self, accelerations, bodies, wrench_guesses, multiple=True)
+
+    def getInverseDynamicsFromPredictions(self, accelerations, bodies, root_frame_wrenches, root_residuals=None):
+        """Skeleton::getInverseDynamicsFromPredictions on the current state: joint torques [B, n] for wrenches on `bodies` given in the
+        root body's frame ([B, E, 6]) and an optional residual wrench on the root ([B, 6])."""
+        from .dynamics import world_inverse_dynamics_from_predictions
+        return world_inverse_dynamics_from_predictions(self, accelerations, bodies, root_frame_wrenches, root_residuals)
+
     def reset_lcp_cache(self):
         self.lcp_cache = None
 

@@ -4,7 +4,10 @@ Atlas-20 and Atlas-33 at B = 4096 and 32768: nbl_inverse_dynamics_forward, nbl_i
 reverse launch of mass_matrix's backward pass, nbl_step_forward (no colliders, record kept), then nbl_forward_dynamics_forward / _backward,
 nbl_inv_mass_matrix and nbl_inv_mass_apply (R = 1) with their ratios to the inverse-dynamics (RNEA) call, next to the dense route to the
 same results through the public functions: torch.linalg.solve(mass_matrix, tau - coriolis_and_gravity) and torch.linalg.inv(mass_matrix)
-(with forward_dynamics / inv_mass_matrix through the same public layer beside them, transposes included on both sides).  HIP events around
+(with forward_dynamics / inv_mass_matrix through the same public layer beside them, transposes included on both sides), then the wrench
+calls with a wrench set on the two feet (E = 2) - nbl_inverse_dynamics_wrench_forward / _backward, nbl_forward_dynamics_wrench_forward /
+_backward in both frames of expression and nbl_contact_inverse_dynamics - each as a ratio to its counterpart without wrenches in the same
+run (the kernels of those calls are the parent commit's: adding the wrench code left their instructions as they were).  HIP events around
 every call on preallocated buffers, 5 warm-up calls, the median of --reps (the new rows also carry the 10th and 90th percentile); one
 JSON line per configuration."""
 import argparse
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 import nimblephysics_amd as na
-from nimblephysics_amd.dynamics import ID_NO_GRAVITY, ID_NO_VELOCITY, _fd_workspace, _workspace
+from nimblephysics_amd.dynamics import CID_MIN_TORQUE, CID_NEAREST, ID_NO_GRAVITY, ID_NO_VELOCITY, WRENCH_WORLD, _fd_workspace, _workspace, _wr_workspace, wrench_set
 
 
 def times_ms(fn, reps, warmup=5):
@@ -101,9 +104,27 @@ def main():
             spread(r, "public_inv_mass_matrix", lambda: na.inv_mass_matrix(w, sb), args.reps)
             r["dense_solve_over_forward_dynamics"] = r["dense_solve_route_ms"] / r["public_forward_dynamics_ms"]
             r["dense_inv_over_inv_mass_matrix"] = r["dense_inv_route_ms"] / r["public_inv_mass_matrix_ms"]
+            # wrenches on the two feet (E = 2), as ratios to the calls without wrenches above
+            feet = wrench_set(w, ["l_foot", "r_foot"])
+            km = feet._device_map(w)
+            Wr = torch.tensor(rng.normal(0, 3.0, (12, B)), device=dev)
+            gW, Wout = torch.empty_like(Wr), torch.empty_like(Wr)
+            wws = _wr_workspace(w, km, B)
+            for tag, fl in (("local", 0), ("world", WRENCH_WORLD)):
+                spread(r, f"id_wrench_forward_{tag}", lambda: L.nbl_inverse_dynamics_wrench_forward(h, km, B, p(s), p(a), p(Wr), fl, p(tau), p(wws), wws.numel(), st), args.reps)
+                spread(r, f"id_wrench_backward_{tag}", lambda: L.nbl_inverse_dynamics_wrench_backward(h, km, B, p(s), p(a), p(Wr), fl, p(g), p(gs), p(ga), p(gW), 0, p(wws), wws.numel(), st), args.reps)
+                spread(r, f"fd_wrench_forward_{tag}", lambda: L.nbl_forward_dynamics_wrench_forward(h, km, B, p(s), p(a), p(Wr), fl, p(acc), p(wws), wws.numel(), st), args.reps)
+                spread(r, f"fd_wrench_backward_{tag}", lambda: L.nbl_forward_dynamics_wrench_backward(h, km, B, p(s), p(a), p(Wr), fl, p(g), p(gs), p(gt1), p(gW), 0, p(wws), wws.numel(), st), args.reps)
+                for k, base in (("id_wrench_forward", "inverse_dynamics_forward"), ("id_wrench_backward", "inverse_dynamics_backward"),
+                                ("fd_wrench_forward", "forward_dynamics_forward"), ("fd_wrench_backward", "forward_dynamics_backward")):
+                    r[f"{k}_{tag}_over_plain"] = r[f"{k}_{tag}_ms"] / r[base + "_ms"]
+            spread(r, "contact_inverse_dynamics_nearest", lambda: L.nbl_contact_inverse_dynamics(h, km, B, p(s), p(a), p(Wr), CID_NEAREST, 0, p(Wout), p(tau), p(wws), wws.numel(), st), args.reps)
+            spread(r, "contact_inverse_dynamics_min_torque", lambda: L.nbl_contact_inverse_dynamics(h, km, B, p(s), p(a), None, CID_MIN_TORQUE, 0, p(Wout), p(tau), p(wws), wws.numel(), st), args.reps)
+            for k in ("contact_inverse_dynamics_nearest", "contact_inverse_dynamics_min_torque"):
+                r[k + "_over_rnea"] = r[k + "_ms"] / r["inverse_dynamics_forward_ms"]
             print(json.dumps(r), flush=True)
             rows.append(r)
-            del w, ws, fws
+            del w, ws, fws, wws, feet
             torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
