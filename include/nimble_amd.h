@@ -234,7 +234,10 @@ const char* nbl_last_error(void);
  *            dynamics quantities, below: appended without a new minor number, like the kinematics entries - the model description did
  *            not change; a caller that needs them looks the symbols up).
  *            + nbl_ik_config, nbl_ik_default_config, nbl_ik_workspace_bytes, nbl_ik_solve (batched inverse kinematics, below: appended
- *            without a new minor number, like the kinematics and dynamics entries). */
+ *            without a new minor number, like the kinematics and dynamics entries).
+ *            + nbl_contact_readout, nbl_contact_readout_rows, nbl_contact_body_wrenches and the NBL_CO_* constants (read-out of a step's
+ *            contacts, impulses and body contact wrenches from its saved record, below: appended without a new minor number, like the
+ *            entries above - neither the model description nor any existing call changed; a caller that needs them looks the symbols up). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -635,6 +638,66 @@ void nbl_ik_default_config(nbl_ik_config* config); /* math::IKConfig's defaults 
 size_t nbl_ik_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B);
 int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* target, const double* q_init, const nbl_ik_config* config,
                      double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- read-out of a step's contacts, impulses and body contact wrenches (csrc/contact_readout.hip) -----------------------------------------
+ * What the contacts of a step WERE, decoded from its saved record (`saved`: the nbl_saved_bytes(m, B) bytes nbl_step_forward wrote; the T
+ * records of a rollout are read with T calls at the byte offsets t * nbl_saved_bytes(m, B) - the rows of a record are interleaved over ITS
+ * B worlds, so one launch cannot take T x B worlds): World::getLastCollisionResult (dart/collision/Contact.hpp:90-147), Contact::force as
+ * ContactConstraint::applyImpulse fills it (ContactConstraint.cpp:630-684), BackpropSnapshot::getContactConstraintImpulses / Mappings.
+ * The calls only read the record: the step, its records and its results are untouched.  All outputs are DEVICE pointers, SoA.
+ *
+ * nbl_contact_readout: count[b] (int32) = the collider contacts of world b.  The pseudo-contacts the record appends after them are not
+ * counted: n_limit_rows[b] joint-limit rows and n_friction_rows[b] joint Coulomb friction rows (either may be NULL).  contacts (may be
+ * NULL) is the table [NBL_CO_FIELDS][C][B], entry ((field * C + slot) * B + b), C = desc.max_contacts of the model (0 when <= 0):
+ *   NBL_CO_POINT (3), NBL_CO_NORMAL (3), NBL_CO_DEPTH, NBL_CO_TYPE (the narrow phase's contact type code)
+ *   NBL_CO_COLLIDER_A, NBL_CO_COLLIDER_B   indices into the description's collider list (box_*)
+ *   NBL_CO_BODY_A, NBL_CO_BODY_B           the colliders' bodies as indices of the description (nbl_kin_map_create's `body`), -1 = the world
+ *   NBL_CO_IMPULSE (3)                     the LCP impulses: normal, tangent 1, tangent 2
+ *   NBL_CO_CLASS (3)                       their row classes: 0 not clamping, 1 clamping, +2 / -2 a friction row on its upper / lower bound
+ *   NBL_CO_FORCE (3)                       (n l0 + t1 l1 + t2 l2) / dt, world coordinates, t1 / t2 = ContactConstraint::getTangentBasisMatrixODE(n)
+ * all as doubles.  A frictionless contact (min(mu_A, mu_B) <= 1e-3) has one LCP row: its tangent impulses read 0 and their classes
+ * NBL_CO_CLASS_EMPTY (-1); its force is along the normal.  Slots at or above count[b] are all zeros.
+ *
+ * nbl_contact_readout_rows: the live LCP rows of every world in the reference's order - constraint by constraint, 3 rows for a contact
+ * with friction, 1 for a frictionless contact, a joint-limit row and a joint-friction row - compacted: n_rows[b] (int32), impulse
+ * [3 C][B] (the reference's sign: a row at an upper joint limit is negative) and mapping [3 C][B] (int32; neural::ConstraintMapping):
+ * -1 clamping, -2 not clamping, >= 0 a friction row on its bound: the compacted index of its contact's normal row.  A joint-limit row
+ * that carries an impulse is clamping; a joint-friction row on its fixed bound has no normal row to point to and reads not clamping.
+ * Rows at or above n_rows[b]: impulse 0, mapping NBL_CO_MAP_NONE.  impulse / mapping may be NULL.
+ *
+ * nbl_contact_body_wrenches: wrench [6 E][B] for E <= NBL_CO_MAX_BODIES bodies of the description (`bodies`, HOST pointer, read during the
+ * call): rows 6 e .. 6 e + 5 = [torque(3); force(3)] in world coordinates, acting at the origin of body e's frame = the sum over the
+ * world's collider contacts of + NBL_CO_FORCE on the body of collider A and - NBL_CO_FORCE on the body of collider B, each with the
+ * moment (point - p_body) x force.  These are the wrenches nbl_forward_dynamics_wrench_forward takes with NBL_WRENCH_WORLD for an all-
+ * NBL_KIN_SPATIAL set with identity offsets on the same bodies.  A body no contact touches gets zeros; a self-collision contact gives
+ * + and - to its two bodies.  Joint-limit and joint-friction rows are generalized forces, not body wrenches: they contribute nothing.
+ * The bodies' world positions are recomputed from the record's q (forward kinematics down each body's ancestor chain), so the call does
+ * not depend on whether or how the record carries tree state (NBL_SAVE_TREE, compact or lane-interleaved).
+ *
+ * A model without a contact stage: count 0, zero tables and wrenches; nothing reads the record.  Errors: NBL_E_BADARG for a null handle,
+ * record or required output (count; n_rows; wrench and bodies when E > 0), B < 0, E < 0 or > NBL_CO_MAX_BODIES, a body index outside
+ * [0, n_bodies) or named twice; nothing is launched then.  B = 0 is a no-op.  Stream-ordered on `stream`, no synchronisation, no atomics,
+ * no workspace; bit-reproducible and independent of B and of a world's place in the batch.  The calls do not use the handle's slices: with
+ * deferred join on, nbl_join_slices first.  No gradients flow through the read-outs (the reference has none there either). */
+#define NBL_CO_POINT 0
+#define NBL_CO_NORMAL 3
+#define NBL_CO_DEPTH 6
+#define NBL_CO_TYPE 7
+#define NBL_CO_COLLIDER_A 8
+#define NBL_CO_COLLIDER_B 9
+#define NBL_CO_BODY_A 10
+#define NBL_CO_BODY_B 11
+#define NBL_CO_IMPULSE 12
+#define NBL_CO_CLASS 15
+#define NBL_CO_FORCE 18
+#define NBL_CO_FIELDS 21
+#define NBL_CO_CLASS_EMPTY -1
+#define NBL_CO_MAP_NONE -4
+#define NBL_CO_MAX_BODIES 64
+int32_t nbl_contact_readout(nbl_model* m, int64_t B, const void* saved, int32_t* count, int32_t* n_limit_rows, int32_t* n_friction_rows,
+                            double* contacts, void* stream);
+int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int32_t* n_rows, double* impulse, int32_t* mapping, void* stream);
+int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream);
 
 /* enabled = 0: off (and reset); 1: HIP events around every kernel launch; N > 1: around the launches of every N-th forward /
  * backward call only (sampling keeps the perturbation of a timed region below 1 %). */

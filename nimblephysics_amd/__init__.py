@@ -11,7 +11,8 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "LossGradient", "LossGradientHighLevelAPI", "NimbleAmdError", "IKMapping", "map_to_pos", "map_to_vel", "MapToPosLayer",
            "MapToVelLayer", "inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics",
            "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "IKConfig", "contact_inverse_dynamics",
-           "inverse_dynamics_from_predictions"]
+           "inverse_dynamics_from_predictions", "read_contacts", "body_contact_wrenches", "rollout_contacts",
+           "rollout_body_contact_wrenches", "ContactReadout"]
 
 
 def __getattr__(name):
@@ -45,6 +46,9 @@ def __getattr__(name):
                 "contact_inverse_dynamics", "inverse_dynamics_from_predictions"):
         from . import dynamics as _d
         return getattr(_d, name)
+    if name in ("read_contacts", "body_contact_wrenches", "rollout_contacts", "rollout_body_contact_wrenches", "ContactReadout"):
+        from . import contacts as _c
+        return getattr(_c, name)
     if name in ("timestep", "TimestepLayer", "rollout", "RolloutLayer"):
         from . import timestep as _t
         return getattr(_t, name)

@@ -27,6 +27,15 @@ ID_JOINT_FORCES = 4
 WRENCH_WORLD = 8      # NBL_WRENCH_WORLD: only the nbl_*_wrench_* calls take it
 CID_SINGLE, CID_NEAREST, CID_MIN_TORQUE = 0, 1, 2   # NBL_CID_*
 
+# NBL_CO_*: the rows of a contact slot in the table of nbl_contact_readout, in order, with their widths
+CO_POINT, CO_NORMAL, CO_DEPTH, CO_TYPE, CO_COLLIDER_A, CO_COLLIDER_B, CO_BODY_A, CO_BODY_B = 0, 3, 6, 7, 8, 9, 10, 11
+CO_IMPULSE, CO_CLASS, CO_FORCE, CO_FIELDS = 12, 15, 18, 21
+CO_FIELD_LIST = (("point", 3), ("normal", 3), ("depth", 1), ("type", 1), ("collider_a", 1), ("collider_b", 1), ("body_a", 1), ("body_b", 1),
+                 ("impulse", 3), ("row_class", 3), ("force", 3))
+CO_CLASS_EMPTY = -1      # the tangent slots of a frictionless contact
+CO_MAP_NONE = -4         # nbl_contact_readout_rows: mapping of a row past the world's live rows
+CO_MAX_BODIES = 64
+
 ST_CONTACT = 0x1
 ST_LCP_STAGE0 = 0x2
 ST_LCP_PIVOT = 0x4

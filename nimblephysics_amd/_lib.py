@@ -156,6 +156,12 @@ def lib():
         getattr(L, f).restype = C.c_int32
     L.nbl_contact_inverse_dynamics.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_size_t, vp]
     L.nbl_contact_inverse_dynamics.restype = C.c_int32
+    L.nbl_contact_readout.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.nbl_contact_readout.restype = C.c_int32
+    L.nbl_contact_readout_rows.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
+    L.nbl_contact_readout_rows.restype = C.c_int32
+    L.nbl_contact_body_wrenches.argtypes = [vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
+    L.nbl_contact_body_wrenches.restype = C.c_int32
     _lib = L
     return L
 
@@ -174,6 +180,7 @@ EXPORTED_SYMBOLS = [
     "nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve",
     "nbl_wrench_workspace_bytes", "nbl_inverse_dynamics_wrench_forward", "nbl_inverse_dynamics_wrench_backward",
     "nbl_forward_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_backward", "nbl_contact_inverse_dynamics",
+    "nbl_contact_readout", "nbl_contact_readout_rows", "nbl_contact_body_wrenches",
 ]
 
 

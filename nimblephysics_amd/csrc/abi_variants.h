@@ -93,6 +93,9 @@
 #define nbl_forward_dynamics_wrench_forward NBL_V(nbl_forward_dynamics_wrench_forward)
 #define nbl_forward_dynamics_wrench_backward NBL_V(nbl_forward_dynamics_wrench_backward)
 #define nbl_contact_inverse_dynamics NBL_V(nbl_contact_inverse_dynamics)
+#define nbl_contact_readout NBL_V(nbl_contact_readout)
+#define nbl_contact_readout_rows NBL_V(nbl_contact_readout_rows)
+#define nbl_contact_body_wrenches NBL_V(nbl_contact_body_wrenches)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

@@ -28,6 +28,7 @@
 #include "kinematics.hip"
 #include "dynamics.hip"
 #include "ik.hip"
+#include "contact_readout.hip"
 
 using namespace NBL_NS;
 
@@ -2048,6 +2049,97 @@ int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double
   hipLaunchKernelGGL(k_ik_solve, dim3((unsigned)((B + IK_BLOCK - 1) / IK_BLOCK)), dim3(IK_BLOCK), 0, (hipStream_t)stream,
                      (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
                      m->nb, m->n, k->P, B, target, q_init, cfg, q_out, loss, steps, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// ---- read-out of a step's contacts, impulses and body contact wrenches from its saved record (csrc/contact_readout.hip) --------------------
+static_assert(CO_POINT == NBL_CO_POINT && CO_NORMAL == NBL_CO_NORMAL && CO_DEPTH == NBL_CO_DEPTH && CO_TYPE == NBL_CO_TYPE &&
+              CO_COLLIDER_A == NBL_CO_COLLIDER_A && CO_COLLIDER_B == NBL_CO_COLLIDER_B && CO_BODY_A == NBL_CO_BODY_A &&
+              CO_BODY_B == NBL_CO_BODY_B && CO_IMPULSE == NBL_CO_IMPULSE && CO_CLASS == NBL_CO_CLASS && CO_FORCE == NBL_CO_FORCE &&
+              CO_FIELDS == NBL_CO_FIELDS && CO_MAX_BODIES == NBL_CO_MAX_BODIES && CO_MAP_NONE == NBL_CO_MAP_NONE, "NBL_CO_* follow contact_readout.hip");
+static int32_t readoutCheck(const nbl_model* m, int64_t B, const void* saved) {
+  if (!m) return fail(NBL_E_BADARG, "null model");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (B > 0 && !saved) return fail(NBL_E_BADARG, "null saved record");
+  if ((B + CO_BLOCK - 1) / CO_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  return NBL_OK;
+}
+static int readoutSlots(const nbl_model* m) { return m->maxContacts > 0 ? m->maxContacts : 0; }
+
+int32_t nbl_contact_readout(nbl_model* m, int64_t B, const void* saved, int32_t* count, int32_t* n_limit_rows, int32_t* n_friction_rows,
+                            double* contacts, void* stream) {
+  const int32_t rc = readoutCheck(m, B, saved);
+  if (rc != NBL_OK) return rc;
+  if (!count) return fail(NBL_E_BADARG, "null count output");
+  if (B == 0) return NBL_OK;
+  DeviceGuard guard(m->device);
+  const int slots = readoutSlots(m);
+  if (!m->hasContact) {   // no contact block in the record: nothing reads it
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)B, (hipStream_t)stream));
+    if (n_limit_rows) HIP_TRY(hipMemsetAsync(n_limit_rows, 0, sizeof(int32_t) * (size_t)B, (hipStream_t)stream));
+    if (n_friction_rows) HIP_TRY(hipMemsetAsync(n_friction_rows, 0, sizeof(int32_t) * (size_t)B, (hipStream_t)stream));
+    if (contacts && slots > 0) HIP_TRY(hipMemsetAsync(contacts, 0, sizeof(double) * (size_t)CO_FIELDS * (size_t)slots * (size_t)B, (hipStream_t)stream));
+    return NBL_OK;
+  }
+  CoBodyTable userOf;                       // device body -> body of the caller's description (the last body of a ball / free chain carries it)
+  for (int i = 0; i < CO_MAX_BODIES; i++) userOf.v[i] = -1;
+  for (int u = 0; u < m->userBodies; u++) userOf.v[m->deviceBody(u)] = (int8_t)u;
+  hipLaunchKernelGGL(k_contact_readout, dim3((unsigned)((B + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, (hipStream_t)stream,
+                     (const DevContactModel*)m->dContact, userOf, m->lay, slots, m->mdl.dt, B, (const double*)saved, count, n_limit_rows,
+                     n_friction_rows, contacts);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int32_t* n_rows, double* impulse, int32_t* mapping, void* stream) {
+  const int32_t rc = readoutCheck(m, B, saved);
+  if (rc != NBL_OK) return rc;
+  if (!n_rows) return fail(NBL_E_BADARG, "null n_rows output");
+  if (B == 0) return NBL_OK;
+  DeviceGuard guard(m->device);
+  const int slots = readoutSlots(m);
+  if (!m->hasContact) {
+    HIP_TRY(hipMemsetAsync(n_rows, 0, sizeof(int32_t) * (size_t)B, (hipStream_t)stream));
+    if (impulse && slots > 0) HIP_TRY(hipMemsetAsync(impulse, 0, sizeof(double) * 3 * (size_t)slots * (size_t)B, (hipStream_t)stream));
+    if (mapping && slots > 0) {
+      const int64_t cnt = 3 * (int64_t)slots * B;
+      hipLaunchKernelGGL(k_contact_fill_i32, dim3((unsigned)((cnt + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, (hipStream_t)stream, mapping, cnt, (int32_t)CO_MAP_NONE);
+      HIP_TRY(hipGetLastError());
+    }
+    return NBL_OK;
+  }
+  hipLaunchKernelGGL(k_contact_readout_rows, dim3((unsigned)((B + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, (hipStream_t)stream,
+                     (const DevContactModel*)m->dContact, m->lay, slots, B, (const double*)saved, n_rows, impulse, mapping);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream) {
+  const int32_t rc = readoutCheck(m, B, saved);
+  if (rc != NBL_OK) return rc;
+  if (E < 0 || E > CO_MAX_BODIES) return fail(NBL_E_BADARG, "a wrench read-out names 0 .. " + std::to_string(CO_MAX_BODIES) + " bodies (got " + std::to_string(E) + ")");
+  if (E > 0 && (!bodies || !wrench)) return fail(NBL_E_BADARG, "null argument");
+  CoBodyTable ent;
+  for (int i = 0; i < CO_MAX_BODIES; i++) ent.v[i] = 0;
+  for (int e = 0; e < E; e++) {
+    if (bodies[e] < 0 || bodies[e] >= m->userBodies)
+      return fail(NBL_E_BADARG, "entry " + std::to_string(e) + ": body " + std::to_string(bodies[e]) + " out of range [0, " + std::to_string(m->userBodies) + ")");
+    for (int f = 0; f < e; f++)
+      if (bodies[f] == bodies[e]) return fail(NBL_E_BADARG, "body " + std::to_string(bodies[e]) + " is named twice (entries " + std::to_string(f) + " and " + std::to_string(e) + ")");
+    const int dev = m->deviceBody(bodies[e]);
+    if (dev < 0 || dev >= CO_MAX_BODIES) {
+      if (m->hasContact) return fail(NBL_E_BADARG, "internal: device body out of range");
+    } else ent.v[e] = (int8_t)dev;
+  }
+  if (B == 0 || E == 0) return NBL_OK;
+  DeviceGuard guard(m->device);
+  if (!m->hasContact) {   // no contacts: zero wrenches, nothing reads the record
+    HIP_TRY(hipMemsetAsync(wrench, 0, sizeof(double) * 6 * (size_t)E * (size_t)B, (hipStream_t)stream));
+    return NBL_OK;
+  }
+  hipLaunchKernelGGL(k_contact_body_wrenches, dim3((unsigned)((B + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevContactModel*)m->dContact, ent, (int)E, m->lay, m->mdl.dt, B, (const double*)saved, wrench);
   HIP_TRY(hipGetLastError());
   return NBL_OK;
 }

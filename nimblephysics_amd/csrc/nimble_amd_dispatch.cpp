@@ -94,7 +94,10 @@
   int32_t nbl_forward_dynamics_wrench_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t,       \
                                                   const double*, double*, double*, double*, int32_t, void*, size_t, void*);                  \
   int32_t nbl_contact_inverse_dynamics##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, int32_t,      \
-                                          double*, double*, void*, size_t, void*);
+                                          double*, double*, void*, size_t, void*);                                                            \
+  int32_t nbl_contact_readout##S(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);                              \
+  int32_t nbl_contact_readout_rows##S(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);                                   \
+  int32_t nbl_contact_body_wrenches##S(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -167,6 +170,9 @@ struct Variant {
   int32_t (*forward_dynamics_wrench_forward)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, double*, void*, size_t, void*);
   int32_t (*forward_dynamics_wrench_backward)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, const double*, double*, double*, double*, int32_t, void*, size_t, void*);
   int32_t (*contact_inverse_dynamics)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, int32_t, double*, double*, void*, size_t, void*);
+  int32_t (*contact_readout)(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);
+  int32_t (*contact_readout_rows)(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);
+  int32_t (*contact_body_wrenches)(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -182,7 +188,7 @@ struct Variant {
    nbl_forward_dynamics_workspace_bytes##S, nbl_forward_dynamics_forward##S, nbl_forward_dynamics_backward##S, nbl_inv_mass_apply##S,       \
    nbl_inv_mass_matrix##S, nbl_wrench_workspace_bytes##S, nbl_inverse_dynamics_wrench_forward##S,                                          \
    nbl_inverse_dynamics_wrench_backward##S, nbl_forward_dynamics_wrench_forward##S, nbl_forward_dynamics_wrench_backward##S,                \
-   nbl_contact_inverse_dynamics##S}
+   nbl_contact_inverse_dynamics##S, nbl_contact_readout##S, nbl_contact_readout_rows##S, nbl_contact_body_wrenches##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -471,6 +477,17 @@ int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t
   NBL_WRENCH_MAP_CHECK(m, k);
   return NBL_FWD(m, contact_inverse_dynamics, k ? k->impl : nullptr, B, state, accel, wrench_guess, mode, flags, wrench_out, tau, workspace,
                  workspace_bytes, stream);
+}
+
+int32_t nbl_contact_readout(nbl_model* m, int64_t B, const void* saved, int32_t* count, int32_t* n_limit_rows, int32_t* n_friction_rows,
+                            double* contacts, void* stream) {
+  return NBL_FWD(m, contact_readout, B, saved, count, n_limit_rows, n_friction_rows, contacts, stream);
+}
+int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int32_t* n_rows, double* impulse, int32_t* mapping, void* stream) {
+  return NBL_FWD(m, contact_readout_rows, B, saved, n_rows, impulse, mapping, stream);
+}
+int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream) {
+  return NBL_FWD(m, contact_body_wrenches, B, saved, E, bodies, wrench, stream);
 }
 
 void nbl_ik_default_config(nbl_ik_config* c) { nbl_ik_default_config_c8(c); }   // (the same in every instantiation)

@@ -131,6 +131,74 @@ class BackpropSnapshot:
     def getPostStepTorques(self): return self.getPreStepTorques()
     def getStatus(self): return self._out(self._status)                                              # NBL_ST_* word per world
 
+    # ---- the step's contacts (contacts.py: csrc/contact_readout.hip; detached, no gradient flows through them) ----
+    def _need_record(self, what):
+        if self._saved is None:
+            raise NimbleAmdError(f"{what}: this snapshot keeps no saved record")
+        return self._saved, int(self._status.shape[0])
+
+    def getContacts(self):
+        """World::getLastCollisionResult of this step: a contacts.ContactReadout (count [B], point / normal / force [B, C, 3], ...) on the
+        World's device, for every world of the snapshot (the batch dimension is kept for a 1-D state too)."""
+        from .contacts import read_contacts
+        saved, B = self._need_record("getContacts()")
+        return read_contacts(self._world, saved, B)
+
+    def getBodyContactWrenches(self, bodies) -> torch.Tensor:
+        """[B, E, 6] ([E, 6] for a 1-D state): the contact wrench [torque; force] on each of `bodies` (names or indices), world coordinates,
+        at the origin of the body's frame (contacts.body_contact_wrenches)."""
+        from .contacts import body_contact_wrenches
+        saved, B = self._need_record("getBodyContactWrenches()")
+        return self._out(body_contact_wrenches(self._world, saved, B, bodies))
+
+    def _rows(self):
+        from .contacts import read_constraint_rows
+        saved, B = self._need_record("the contact constraints")
+        if getattr(self, "_rows_cache", None) is None:
+            self._rows_cache = read_constraint_rows(self._world, saved, B)
+        return self._rows_cache
+
+    def _per_world(self, values: torch.Tensor, keep: torch.Tensor):
+        """rows [B, R] + a mask -> what the reference returns per world: a LIST of B 1-D tensors (the worlds differ in length); the one
+        tensor itself for a 1-D state"""
+        out = [values[b][keep[b]] for b in range(values.shape[0])]
+        return out[0] if self._one_d else out
+
+    def _live(self):
+        n_rows, imp, mp = self._rows()
+        return torch.arange(imp.shape[1], device=imp.device)[None, :] < n_rows[:, None]
+
+    def getNumContacts(self):
+        """BackpropSnapshot::getNumContacts (BackpropSnapshot.cpp:1685-1693): the number of constraint ROWS of the step's LCP - three per
+        contact with friction, one per frictionless contact, joint-limit row and joint-friction row - per world: [B] int32 (an int for a
+        1-D state).  The number of collider contacts is getContacts().count."""
+        n = self._rows()[0]
+        return int(n[0]) if self._one_d else n
+
+    def getNumClamping(self):
+        """Rows classified clamping, per world ([B] int64; an int for a 1-D state)."""
+        c = ((self._rows()[2] == -1) & self._live()).sum(dim=1)
+        return int(c[0]) if self._one_d else c
+
+    def getNumUpperBound(self):
+        """Friction rows on their bound, per world ([B] int64; an int for a 1-D state)."""
+        c = ((self._rows()[2] >= 0) & self._live()).sum(dim=1)
+        return int(c[0]) if self._one_d else c
+
+    def getContactConstraintImpulses(self):
+        """BackpropSnapshot::getContactConstraintImpulses: the impulses of the live rows in the reference's order (see getNumContacts), the
+        joint-limit and joint-friction rows included, in the reference's sign.  A list of B 1-D tensors (one tensor for a 1-D state)."""
+        return self._per_world(self._rows()[1], self._live())
+
+    def getContactConstraintMappings(self):
+        """BackpropSnapshot::getContactConstraintMappings: per live row -1 clamping, -2 not clamping, >= 0 a friction row on its bound (the
+        row of its contact's normal).  A list of B 1-D int32 tensors (one tensor for a 1-D state)."""
+        return self._per_world(self._rows()[2], self._live())
+
+    def getClampingConstraintImpulses(self):
+        """BackpropSnapshot::getClampingConstraintImpulses: the impulses of the clamping rows, in row order; a list like the above."""
+        return self._per_world(self._rows()[1], (self._rows()[2] == -1) & self._live())
+
     def _check(self, world):
         """The record is read against the model constants of the world that is passed in: the world that took the snapshot, or one
         with the same model on the same device (a `clone()`; the reference's snapshots are likewise used with clones of their world,

@@ -93,6 +93,7 @@ class World:
         self.m = self._L.nbl_model_lcp_rows(self._h)
         self.lcp_cache = None
         self._ws, self._ws_B, self._scratch_saved = None, 0, None
+        self._last_record = None
         self._uploaded_inertia = [(float(b.mass), tuple(float(x) for x in b.com), tuple(float(x) for x in b.inertia)) for b in self.model.bodies]
 
     def _destroy_handle(self):
@@ -424,6 +425,7 @@ class World:
             self.lcp_cache = cache_out
         self.last_status = status
         self._last_saved = saved if want_saved else None
+        self._last_record = saved               # (the reusable contact scratch of World.step included: getLastCollisionResult reads it)
         return nxt, (saved if want_saved else None), status
 
     def backward_soa(self, saved: torch.Tensor, grad_next: torch.Tensor):
@@ -647,6 +649,27 @@ class World:
         """World::step on the stored state/action (no gradient bookkeeping kept)."""
         nxt, _, _ = self.step_soa(self._state, self._action, want_saved=False)
         self._state = nxt
+
+    def getLastCollisionResult(self):
+        """World::getLastCollisionResult: the contacts of the last step() / timestep() / forwardPass() on this World, as a
+        contacts.ContactReadout (count [B], point / normal / force [B, C, 3], depth, type, colliders, bodies, impulses, row classes).
+        World.step() keeps one reusable record per World: read it before the next step.  A model without colliders reports count 0.
+        Detached: no gradient flows through it."""
+        from .contacts import ContactReadout, read_contacts
+        if self.last_status is None or self.last_status.dim() != 1:
+            raise NimbleAmdError("getLastCollisionResult(): no step has been taken on this World")
+        B = int(self.last_status.shape[0])
+        rec = getattr(self, "_last_record", None)
+        if rec is None:                          # World.step() on a model without a contact stage keeps no record: there is nothing to read
+            if self.m > 0:
+                raise NimbleAmdError("getLastCollisionResult(): the last step kept no record")
+            Cn, dev = max(int(self.model.max_contacts), 0), self.device
+            z = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+            return ContactReadout(count=z(B, dt=torch.int32), n_limit_rows=z(B, dt=torch.int32), n_friction_rows=z(B, dt=torch.int32),
+                                  point=z(B, Cn, 3), normal=z(B, Cn, 3), force=z(B, Cn, 3), impulse=z(B, Cn, 3), row_class=z(B, Cn, 3),
+                                  depth=z(B, Cn), type=z(B, Cn), collider_a=z(B, Cn, dt=torch.int64), collider_b=z(B, Cn, dt=torch.int64),
+                                  body_a=z(B, Cn, dt=torch.int64), body_b=z(B, Cn, dt=torch.int64))
+        return read_contacts(self, rec, B)
 
     # ---- deferred join: one handle, slices that are not joined per call (nbl_set_deferred_join, include/nimble_amd.h) ----
     def set_deferred_join(self, enabled: bool = True):
