@@ -76,6 +76,10 @@ struct CoopLds {
   double vec[4][MAXR];         // vector broadcast scratch
   int perm[MAXR];
   int pad[4];
+#ifdef NBL_CASCADE_TIMING
+  unsigned long long tstat[16];   // developer stamps: cycles of this world's standardisation loop, part by part (LP_* below).  Zeroed and read by
+                                  // coopStage0 / k_contact_solve_coop only: the loops of the cascade kernels add to it and nobody looks
+#endif
 };
 static_assert(sizeof(CoopLds) % 16 == 0, "CoopLds must keep 16-byte alignment in an array");
 
@@ -204,17 +208,29 @@ DEV void coopIdentityColumn(double (&a)[MAXR], int eIn) {
 }
 
 DEV double coopRsqrt(double x);
+// Developer stamps of the standardisation loop (tools/cascade_timing.py): every world sums the cycles of the parts of ITS loop in
+// CoopLds::tstat; k_contact_solve_coop adds them to g_routeStat under the route the world took, so that a route's loop is accounted
+// for part by part.  LP_PINV is the whole of coopPinvOfQ; LP_QR .. LP_ZW are the parts of the Householder route inside it.
+enum { LP_CLASSIFY = 0, LP_BUILDQ = 1, LP_QR = 2, LP_R1INV = 3, LP_WWT = 4, LP_CHOL = 5, LP_SUBST = 6, LP_ZW = 7, LP_PINV = 8, LP_APPLY = 9,
+       LP_UPDATE = 10, LP_VALID = 11, LP_ITERS = 12, LP_FACTS = 13, LP_WORLDS = 14, LP_LOOP = 15, LP_COUNT = 16 };
 #if defined(NBL_CASCADE_TIMING) && defined(__HIPCC__)
 __device__ unsigned long long g_pinvStat[8];   // developer counters of the Householder route (tools/cascade_timing.py): calls, cycles of the parts
+__device__ unsigned long long g_routeStat[4 * LP_COUNT];   // [route][LP_*]: guess rows / Cholesky / Householder full rank / Householder rank deficient
 #endif
 #if defined(NBL_CASCADE_TIMING) && defined(__HIP_DEVICE_COMPILE__)
 #define PINV_T0() long long pvT = clock64()
-#define PINV_ADD(k) do { const long long pvN = clock64(); if (ln == 0) atomicAdd(&g_pinvStat[k], (unsigned long long)(pvN - pvT)); pvT = pvN; } while (0)
+#define PINV_ADD(k) do { const long long pvN = clock64(); if (ln == 0) { atomicAdd(&g_pinvStat[k], (unsigned long long)(pvN - pvT)); S.tstat[LP_QR - 1 + (k)] += (unsigned long long)(pvN - pvT); } pvT = pvN; } while (0)
 #define PINV_CNT(k) do { if (ln == 0) atomicAdd(&g_pinvStat[k], 1ull); } while (0)
+#define LOOP_T0() long long lpT = clock64()
+#define LOOP_ADD(k) do { const long long lpN = clock64(); if (w.lane() == 0) S.tstat[k] += (unsigned long long)(lpN - lpT); lpT = lpN; } while (0)
+#define LOOP_CNT(k) do { if (w.lane() == 0) S.tstat[k] += 1ull; } while (0)
 #else
 #define PINV_T0() do { } while (0)
 #define PINV_ADD(k) do { } while (0)
 #define PINV_CNT(k) do { } while (0)
+#define LOOP_T0() do { } while (0)
+#define LOOP_ADD(k) do { } while (0)
+#define LOOP_CNT(k) do { } while (0)
 #endif
 
 // S.P <- pseudo-inverse of the MAXR x MAXR matrix whose column j is a[] of lane j (< MAXR) (masked rows/columns zero);
@@ -865,31 +881,42 @@ DEV void coopBuildQ(const W& w, CoopLds& S, const CoopRow& R, const CoopClasses&
   const int ln = w.lane();
   const bool colOn = ln < MAXR && K.cls == RC_CLAMPING;
   const double* Ac = R.fresh();
-  double e1 = 0.0, e2 = 0.0;
-  if (K.nu > 0) {
-    // stage A in LDS so that a normal column can add its contact's upper-bound friction columns
+  if (K.nu == 0) {
+    // Q is the clamping block of A itself (CGGM.cpp:256-266, couplings included)
 #pragma unroll
-    for (int i = 0; i < MAXR; i++) if (ln < MAXR) S.R[i * CLD + ln] = R.a(Ac, i);
-    const double E1 = w.shfl(K.E, ln + 1), E2 = w.shfl(K.E, ln + 2);
-    if (!R.fric && ln + 2 < MAXR) {
-      if ((K.ubMask >> (ln + 1)) & 1u) e1 = E1;
-      if ((K.ubMask >> (ln + 2)) & 1u) e2 = E2;
+    for (int i = 0; i < MAXR; i++) {
+      double q = R.a(Ac, i);
+      if (i == ln) q += cfm;
+      a[i] = (colOn && ((K.clampMask >> i) & 1u)) ? q : 0.0;
     }
-    w.sync();
+    return;
   }
+  // A friction row on its bound.  This lane's column of A is read once, in one batch with no branch between the reads (24 L2 round trips in
+  // flight together, not waited for one by one), into the registers that end up holding the column of Q; from there it goes to LDS, so
+  // that a normal column can add its contact's upper-bound friction columns.
+#pragma unroll
+  for (int i = 0; i < MAXR; i++) a[i] = R.a(Ac, i);
+#pragma unroll
+  for (int i = 0; i < MAXR; i++) if (ln < MAXR) S.R[i * CLD + ln] = a[i];
+  double e1 = 0.0, e2 = 0.0;
+  const double E1 = w.shfl(K.E, ln + 1), E2 = w.shfl(K.E, ln + 2);
+  if (!R.fric && ln + 2 < MAXR) {
+    if ((K.ubMask >> (ln + 1)) & 1u) e1 = E1;
+    if ((K.ubMask >> (ln + 2)) & 1u) e2 = E2;
+  }
+  w.sync();
   const int c1 = (ln + 1 < MAXR) ? ln + 1 : 0, c2 = (ln + 2 < MAXR) ? ln + 2 : 0;
 #pragma unroll
   for (int i = 0; i < MAXR; i++) {
-    double q = R.a(Ac, i);
-    if (K.nu > 0) q = fma(e2, S.R[i * CLD + c2], fma(e1, S.R[i * CLD + c1], q));
+    double q = fma(e2, S.R[i * CLD + c2], fma(e1, S.R[i * CLD + c1], a[i]));
     // The reference forms Q = A_c^T M^-1 (A_c + A_ub E) from constraint-force columns when a friction row sits on its bound, and a
     // joint-limit constraint has none (a DifferentiableContactConstraint without a contact: zero world force, DCC.cpp:51-99): its row
-    // and column of Q are zero.  (Without upper-bound rows Q is the clamping block of A itself, CGGM.cpp:256-266, couplings included.)
-    if (K.nu > 0 && (R.lim || ((R.limMask >> i) & 1u))) q = 0.0;
+    // and column of Q are zero.
+    if (R.lim || ((R.limMask >> i) & 1u)) q = 0.0;
     if (i == ln) q += cfm;
     a[i] = (colOn && ((K.clampMask >> i) & 1u)) ? q : 0.0;
   }
-  if (K.nu > 0) w.sync();   // reads of the staged A complete before the factorisation reuses the buffer
+  w.sync();   // reads of the staged A complete before the factorisation reuses the buffer
 }
 
 // Q^+ of the Q that coopBuildQ left in a[]: without upper-bound rows Q = A(clamping, clamping) + cfm I is symmetric positive
@@ -919,26 +946,34 @@ DEV bool coopStandardizeLoop(const W& w, CoopLds& S, const CoopRow& R, double& X
                              RowMask guessMask, bool& pinvValid, CoopClasses& K) {
   double a[MAXR];
   bool ok = false;
+  LOOP_T0();
 #pragma unroll 1
   for (int iter = 0; iter < MAXR + 1; iter++) {
+    LOOP_CNT(LP_ITERS);
     coopClassify(w, R, X, ignoreFriction, K);
+    LOOP_ADD(LP_CLASSIFY);
     if (K.nc == 0) {
       pinvValid = false;
       ok = coopValid(w, S, R, 0.0, ignoreFriction, cfm, 1);
       if (ok) X = 0.0;
+      LOOP_ADD(LP_VALID);
       break;
     }
     double fc;
     if (iter == 0 && K.nu == 0 && guessMask != 0 && K.clampMask == guessMask) fc = X;
     else {
+      LOOP_CNT(LP_FACTS);
       coopBuildQ(w, S, R, K, cfm, a);
+      LOOP_ADD(LP_BUILDQ);
 #ifdef NBL_CASCADE_TIMING
       K.dbgRank = coopPinvOfQ(w, a, S, K);
 #else
       coopPinvOfQ(w, a, S, K);
 #endif
+      LOOP_ADD(LP_PINV);
       fc = coopPinvApply<W, false>(w, S, K.cls == RC_CLAMPING ? R.Bv : 0.0, 0);
       pinvValid = true;
+      LOOP_ADD(LP_APPLY);
     }
     double newX = 0.0;
     bool newlyNot = false;
@@ -951,7 +986,10 @@ DEV bool coopStandardizeLoop(const W& w, CoopLds& S, const CoopRow& R, double& X
       const double clean = (fabs(om - R.mu) < fabs(om + R.mu)) ? R.mu : -R.mu;
       newX = fcN * clean;
     }
-    if (!coopValid(w, S, R, newX, ignoreFriction, cfm, 1)) { ok = false; break; }
+    LOOP_ADD(LP_UPDATE);
+    const bool valid = coopValid(w, S, R, newX, ignoreFriction, cfm, 1);
+    LOOP_ADD(LP_VALID);
+    if (!valid) { ok = false; break; }
     X = newX;
     ok = true;
     if (w.ballot(newlyNot) == 0ull) break;
@@ -991,6 +1029,8 @@ DEV void coopStage0(const W& w, CoopLds& S, const CoopRow& R, bool haveCache, do
   out.X0 = X;
 #if defined(NBL_CASCADE_TIMING) && defined(__HIP_DEVICE_COMPILE__)
   out.tGuess = clock64();
+  if (ln < LP_COUNT) S.tstat[ln] = 0ull;
+  w.sync();
 #endif
   CoopClasses K;
   const bool ok = coopStandardizeLoop(w, S, R, X, 0.0, false, guessMask, pinvValid, K);

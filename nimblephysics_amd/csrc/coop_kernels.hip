@@ -223,6 +223,14 @@ __global__ __launch_bounds__(64) NBL_WAVES(NBL_W_SOLVE) void k_contact_solve_coo
       lws[(int64_t)(LW_STAGE_CYCLES + 7) * B + b] = (double)out.nu;
       lws[(int64_t)(LW_STAGE_CYCLES + 8) * B + b] = (double)out.fast;
     }
+    if (m > 0) {   // this world's loop, part by part, under its route (the tool's four routes: guess rows / Cholesky / Householder full rank / rank deficient)
+      const long long loopCycles = clock64() - out.tGuess;
+      const int route = out.fast == 1 ? 0 : ((out.nu % 100) == 0 ? 1 : (out.fast == 2 ? 3 : 2));
+      w.sync();
+      if (ln < LP_WORLDS) atomicAdd(&g_routeStat[route * LP_COUNT + ln], S.tstat[ln]);
+      if (ln == LP_WORLDS) atomicAdd(&g_routeStat[route * LP_COUNT + ln], 1ull);
+      if (ln == LP_LOOP) atomicAdd(&g_routeStat[route * LP_COUNT + ln], (unsigned long long)loopCycles);
+    }
 #endif
     if (out.ok) {
       const uint32_t nanBit = coopContactOutputs(w, S, R, n, m, out.X, out.K, 0.0, out.pinvValid, saved, lay, dn, cacheOut, nv, B, b);

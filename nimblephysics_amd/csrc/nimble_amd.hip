@@ -1314,6 +1314,12 @@ int32_t nbl_debug_dantzig_stats(unsigned long long* out16, int32_t reset) {
                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dzStatSlow), z, sizeof(z))); }
   return NBL_OK;
 }
+int32_t nbl_debug_route_stats(unsigned long long* out64, int32_t reset) {   // the stage-0 standardisation loop per route and part (coop_dev.hpp, LP_*)
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_routeStat), sizeof(unsigned long long) * 4 * LP_COUNT));
+  if (reset) { unsigned long long z[4 * LP_COUNT] = {0}; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_routeStat), z, sizeof(z))); }
+  return NBL_OK;
+}
 int32_t nbl_debug_dantzig_stats_slow(unsigned long long* out16) {   // the same sums over the solves of more than NBL_DZ_SLOW cycles
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_dzStatSlow), sizeof(unsigned long long) * 16));

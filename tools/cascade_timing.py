@@ -22,6 +22,8 @@ import ctypes
 L = _lib.lib()
 buf = (ctypes.c_ulonglong * 24)()
 L.nbl_debug_dantzig_stats(buf, 1)
+if hasattr(L, "nbl_debug_route_stats"):
+    L.nbl_debug_route_stats((ctypes.c_ulonglong * 64)(), 1)
 nxt, saved, status = world.step_soa(st, at)
 torch.cuda.synchronize()
 L.nbl_debug_dantzig_stats(buf, 0)
@@ -46,6 +48,29 @@ pv = dz[16:24]
 if pv[0]:
     print(f"Householder route: {pv[0]} factorisations; cycles each: pivoted QR {pv[1] / pv[0]:.0f}, R1^-1 [R2 | G1] {pv[2] / pv[0]:.0f}, W W^T {pv[3] / pv[0]:.0f}, "
           f"Cholesky of I + W W^T {pv[4] / pv[0]:.0f}, two substitutions {pv[5] / pv[0]:.0f}, [z; W^T z] {pv[6] / pv[0]:.0f}")
+# The stage-0 standardisation loop, route by route and part by part (coop_dev.hpp, LP_*): what a world of each route spends where.
+if hasattr(L, "nbl_debug_route_stats"):
+    rb = (ctypes.c_ulonglong * 64)()
+    L.nbl_debug_route_stats(rb, 0)
+    rs = np.array(list(rb), dtype=np.float64).reshape(4, 16)
+    parts = [("classification", 0), ("building Q", 1), ("pseudo-inverse: pivoted QR", 2), ("pseudo-inverse: R1^-1 [R2 | G1]", 3), ("pseudo-inverse: W W^T", 4),
+             ("pseudo-inverse: Cholesky of I + W W^T", 5), ("pseudo-inverse: two substitutions", 6), ("pseudo-inverse: [z; W^T z]", 7),
+             ("pseudo-inverse: the rest (Cholesky route, full-rank back substitution, entry / exit)", -1), ("applying the pseudo-inverse", 9),
+             ("new x (the loop's bookkeeping)", 10), ("validity test", 11)]
+    routes = ["guess rows", "Cholesky", "Householder, full rank", "Householder, rank deficient"]
+    print("stage-0 standardisation loop, cycles per world of each route (k_contact_solve_coop):")
+    print(f"  {'part':86s}" + "".join(f"{r:>30s}" for r in routes))
+    nw = np.maximum(rs[:, 14], 1)
+    for nme, k in parts:
+        col = rs[:, 8] - rs[:, 2:8].sum(1) if k < 0 else rs[:, k]
+        print(f"  {nme:86s}" + "".join(f"{c / n_:30.0f}" for c, n_ in zip(col, nw)))
+    acc = rs[:, [0, 1, 8, 9, 10, 11]].sum(1)
+    print(f"  {'sum of the parts':86s}" + "".join(f"{c / n_:30.0f}" for c, n_ in zip(acc, nw)))
+    print(f"  {'the whole loop (guess stamp to the end of stage 0)':86s}" + "".join(f"{c / n_:30.0f}" for c, n_ in zip(rs[:, 15], nw)))
+    print(f"  {'not attributed (stamps, loop entry and exit)':86s}" + "".join(f"{(t - c) / n_:30.0f}" for t, c, n_ in zip(rs[:, 15], acc, nw)))
+    print(f"  {'worlds':86s}" + "".join(f"{int(n_):30d}" for n_ in rs[:, 14]))
+    print(f"  {'loop iterations per world':86s}" + "".join(f"{c / n_:30.2f}" for c, n_ in zip(rs[:, 12], nw)))
+    print(f"  {'factorisations per world':86s}" + "".join(f"{c / n_:30.2f}" for c, n_ in zip(rs[:, 13], nw)))
 stat = status.cpu().numpy()
 ws = world._workspace(B).view(torch.float64).cpu().numpy()
 nb = 15
