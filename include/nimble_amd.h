@@ -237,7 +237,10 @@ const char* nbl_last_error(void);
  *            without a new minor number, like the kinematics and dynamics entries).
  *            + nbl_contact_readout, nbl_contact_readout_rows, nbl_contact_body_wrenches and the NBL_CO_* constants (read-out of a step's
  *            contacts, impulses and body contact wrenches from its saved record, below: appended without a new minor number, like the
- *            entries above - neither the model description nor any existing call changed; a caller that needs them looks the symbols up). */
+ *            entries above - neither the model description nor any existing call changed; a caller that needs them looks the symbols up).
+ *            + nbl_body_set_create, nbl_body_set_destroy, nbl_body_set_mass, nbl_body_set_origin_moments, nbl_centroidal_workspace_bytes,
+ *            nbl_centroidal_forward, nbl_centroidal_backward and the NBL_CEN_* flags (centre of mass, momentum and energy of a body set,
+ *            below: appended without a new minor number, like the entries above). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -698,6 +701,64 @@ int32_t nbl_contact_readout(nbl_model* m, int64_t B, const void* saved, int32_t*
                             double* contacts, void* stream);
 int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int32_t* n_rows, double* impulse, int32_t* mapping, void* stream);
 int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream);
+
+/* ---- centre of mass, momentum and energy of a body set (csrc/centroidal.hip) -----------------------------------------------------------------
+ * The whole-body quantities of Skeleton (dart/dynamics/Skeleton.cpp:13598-13810; python/_nimblephysics/dynamics/Skeleton.cpp:1873-2035)
+ * for B worlds, one world per lane, one launch for whichever outputs are asked for, and their exact vector-Jacobian product.  Appended
+ * within ABI minor 5 like the entries above: a caller that needs them looks the symbols up.
+ *
+ * A BODY SET (nbl_body_set_create) names bodies of the description the model was created from (`bodies`: `count` indices there, each at
+ * most once; NULL with count 0: every body of the model - a Skeleton of the reference is the set of its bodies).  The library resolves its
+ * internal bodies (a ball / free chain carries its mass on the body that carries T_cj).  A model of more than 64 internal bodies is
+ * NBL_E_UNSUPPORTED; an index out of range or named twice, and a set whose total mass is 0, are NBL_E_BADARG.  Destroy a set before the
+ * model it was made for.  nbl_body_set_mass: the set's total mass at the handle's CURRENT inertias (Skeleton::getMass, Skeleton.cpp:11310).
+ * A null handle or a set made for another model: 0 and nbl_last_error() says why.
+ *
+ * nbl_centroidal_forward writes every output that is not NULL (device pointers, SoA like the step's; state [2n][B] = [q; v]):
+ *   com      [3][B]    sum m_i (p_i + R_i c_i) / M                                          Skeleton::getCOM (Skeleton.cpp:13645-13658)
+ *   com_vel  [3][B]    sum m_i d/dt(p_i + R_i c_i) / M, world coordinates                   getCOMLinearVelocity(World, World) (:13695-13701)
+ *   com_acc  [3][B]    sum m_i d2/dt2(p_i + R_i c_i) / M at the accelerations accel [n][B]: the classical linear acceleration of every
+ *                      body's centre of mass (BodyNode::getCOMLinearAcceleration); gravity is NOT part of it  getCOMLinearAcceleration (:13714-13720)
+ *   momentum [6][B]    [angular momentum about the set's centre of mass; linear momentum], world coordinates.  The reference has the momenta
+ *                      PER BODY only (BodyNode::getLinearMomentum / getAngularMomentum, BodyNode.cpp:2378-2391): their sum over the set is
+ *                      this library's extension.  The linear part equals M com_vel and is computed independently from G_i V_i.
+ *   ke       [B]       sum V_i^T G_i V_i / 2                                                computeKineticEnergy (:13598-13607; BodyNode.cpp:2357-2363)
+ *   pe       [B]       - sum m_i g . (p_i + R_i c_i) + sum_d k_d (q_d - rest_d)^2 / 2 over the coordinates of the set's joints
+ *                      (computePotentialEnergy, :13610-13621; GenericJoint.hpp:1598-1610).  NBL_CEN_PE_BODY_ORIGIN: - sum m_i g . p_i instead, the reference's number
+ *                      (BodyNode::computePotentialEnergy, BodyNode.cpp:2372-2375, takes the body frame's origin, not its centre of mass);
+ *                      NBL_CEN_NO_SPRINGS leaves the spring energy out.
+ *   Jcom     [3 n][B]  row-major 3 x n per world: getCOMLinearJacobian in world coordinates (:13783-13790), com_vel = Jcom v.  The columns
+ *                      of coordinates that move no body of the set are zeros, written by the kernel (no host zero-fill).
+ * All read the handle's CURRENT inertias (nbl_set_body_inertia(s), nbl_set_inertia_params).  accel may be NULL unless com_acc is asked for.
+ *
+ * nbl_centroidal_backward: grad_state [2n][B] and grad_accel [n][B] (either may be NULL) = (accumulate: +=) the cotangents g_* (any may be
+ * NULL: it contributes nothing) pulled back.  Exact in both blocks of the state: the velocity- and acceleration-level outputs carry their
+ * full dependence on the positions; free and ball coordinates are differentiated analytically through expMapJac.  Jcom has no cotangent.
+ *
+ * workspace: nbl_centroidal_workspace_bytes(m, B) bytes of device scratch (54 doubles per body and world; one size serves both calls);
+ * calls that share a workspace must be ordered on one stream.  Errors: NBL_E_BADARG (null handle / set / state / workspace, a set made for
+ * another model, B < 0, unknown flag bits, com_acc or g_com_acc without accel, a set whose mass has become 0), NBL_E_WORKSPACE; nothing is
+ * launched then.  B = 0 is a no-op.  B may be (T + 1) x worlds.  Stream-ordered on `stream`, no synchronisation, no atomics, no LDS:
+ * bit-reproducible and independent of B and of a world's place in the batch.  The calls do not use the handle's slices. */
+#define NBL_CEN_PE_BODY_ORIGIN 1 /* pe from the body frames' origins (the reference's rule) instead of the bodies' centres of mass */
+#define NBL_CEN_NO_SPRINGS 2     /* pe without the joint spring energy */
+typedef struct nbl_body_set nbl_body_set; /* opaque */
+int32_t nbl_body_set_create(nbl_model* m, int32_t count, const int32_t* bodies, nbl_body_set** out);
+void nbl_body_set_destroy(nbl_body_set* s);
+double nbl_body_set_mass(nbl_model* m, const nbl_body_set* s);
+/* For a caller that merged welded BodyNodes before nbl_model_create and wants NBL_CEN_PE_BODY_ORIGIN to give the reference's number on
+ * them: moments [count][3] (HOST pointer) = for each of `bodies`, sum_k m_k o_k over the BodyNodes merged into it, o_k the origin of
+ * BodyNode k's frame in the merged body's frame.  pe then reads - sum g . (m_i p_i + R_i moment_i).  Default: zeros (the body's own origin).
+ * Takes effect for the calls issued afterwards; the caller repeats it when those masses change. */
+int32_t nbl_body_set_origin_moments(nbl_model* m, nbl_body_set* s, int32_t count, const int32_t* bodies, const double* moments);
+size_t nbl_centroidal_workspace_bytes(const nbl_model* m, int64_t B);
+int32_t nbl_centroidal_forward(nbl_model* m, const nbl_body_set* s, int64_t B, const double* state, const double* accel, int32_t flags,
+                               double* com, double* com_vel, double* com_acc, double* momentum, double* ke, double* pe, double* Jcom,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* s, int64_t B, const double* state, const double* accel, int32_t flags,
+                                const double* g_com, const double* g_com_vel, const double* g_com_acc, const double* g_momentum,
+                                const double* g_ke, const double* g_pe, double* grad_state, double* grad_accel, int32_t accumulate,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* enabled = 0: off (and reset); 1: HIP events around every kernel launch; N > 1: around the launches of every N-th forward /
  * backward call only (sampling keeps the perturbation of a timed region below 1 %). */

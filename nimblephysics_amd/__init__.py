@@ -12,7 +12,8 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "MapToVelLayer", "inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics",
            "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "IKConfig", "contact_inverse_dynamics",
            "inverse_dynamics_from_predictions", "read_contacts", "body_contact_wrenches", "rollout_contacts",
-           "rollout_body_contact_wrenches", "ContactReadout"]
+           "rollout_body_contact_wrenches", "ContactReadout", "center_of_mass", "com_velocity", "com_acceleration", "centroidal_momentum",
+           "kinetic_energy", "potential_energy", "com_jacobian", "centroidal", "Centroidal"]
 
 
 def __getattr__(name):
@@ -49,6 +50,11 @@ def __getattr__(name):
     if name in ("read_contacts", "body_contact_wrenches", "rollout_contacts", "rollout_body_contact_wrenches", "ContactReadout"):
         from . import contacts as _c
         return getattr(_c, name)
+    if name in ("center_of_mass", "com_velocity", "com_acceleration", "centroidal_momentum", "kinetic_energy", "potential_energy", "com_jacobian",
+                "centroidal", "Centroidal"):
+        import importlib                                    # (not `from . import`: "centroidal" is also the name asked for here)
+        _cen = importlib.import_module(".centroidal", __name__)
+        return _cen if name == "centroidal" else getattr(_cen, name)       # the module answers a call like its function centroidal()
     if name in ("timestep", "TimestepLayer", "rollout", "RolloutLayer"):
         from . import timestep as _t
         return getattr(_t, name)

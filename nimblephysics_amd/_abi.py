@@ -35,6 +35,8 @@ CO_FIELD_LIST = (("point", 3), ("normal", 3), ("depth", 1), ("type", 1), ("colli
 CO_CLASS_EMPTY = -1      # the tangent slots of a frictionless contact
 CO_MAP_NONE = -4         # nbl_contact_readout_rows: mapping of a row past the world's live rows
 CO_MAX_BODIES = 64
+# nbl_centroidal_forward / _backward flags (NBL_CEN_*)
+CEN_PE_BODY_ORIGIN, CEN_NO_SPRINGS = 1, 2
 
 ST_CONTACT = 0x1
 ST_LCP_STAGE0 = 0x2

@@ -162,6 +162,20 @@ def lib():
     L.nbl_contact_readout_rows.restype = C.c_int32
     L.nbl_contact_body_wrenches.argtypes = [vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
     L.nbl_contact_body_wrenches.restype = C.c_int32
+    L.nbl_body_set_create.argtypes = [vp, C.c_int32, vp, C.POINTER(vp)]
+    L.nbl_body_set_create.restype = C.c_int32
+    L.nbl_body_set_destroy.argtypes = [vp]
+    L.nbl_body_set_destroy.restype = None
+    L.nbl_body_set_mass.argtypes = [vp, vp]
+    L.nbl_body_set_mass.restype = C.c_double
+    L.nbl_body_set_origin_moments.argtypes = [vp, vp, C.c_int32, vp, vp]
+    L.nbl_body_set_origin_moments.restype = C.c_int32
+    L.nbl_centroidal_workspace_bytes.argtypes = [vp, C.c_int64]
+    L.nbl_centroidal_workspace_bytes.restype = C.c_size_t
+    L.nbl_centroidal_forward.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_centroidal_forward.restype = C.c_int32
+    L.nbl_centroidal_backward.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_centroidal_backward.restype = C.c_int32
     _lib = L
     return L
 
@@ -181,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "nbl_wrench_workspace_bytes", "nbl_inverse_dynamics_wrench_forward", "nbl_inverse_dynamics_wrench_backward",
     "nbl_forward_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_backward", "nbl_contact_inverse_dynamics",
     "nbl_contact_readout", "nbl_contact_readout_rows", "nbl_contact_body_wrenches",
+    "nbl_body_set_create", "nbl_body_set_destroy", "nbl_body_set_mass", "nbl_body_set_origin_moments", "nbl_centroidal_workspace_bytes", "nbl_centroidal_forward", "nbl_centroidal_backward",
 ]
 
 

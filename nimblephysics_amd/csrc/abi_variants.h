@@ -96,6 +96,14 @@
 #define nbl_contact_readout NBL_V(nbl_contact_readout)
 #define nbl_contact_readout_rows NBL_V(nbl_contact_readout_rows)
 #define nbl_contact_body_wrenches NBL_V(nbl_contact_body_wrenches)
+#define nbl_body_set NBL_V(nbl_body_set)
+#define nbl_body_set_create NBL_V(nbl_body_set_create)
+#define nbl_body_set_destroy NBL_V(nbl_body_set_destroy)
+#define nbl_body_set_mass NBL_V(nbl_body_set_mass)
+#define nbl_body_set_origin_moments NBL_V(nbl_body_set_origin_moments)
+#define nbl_centroidal_workspace_bytes NBL_V(nbl_centroidal_workspace_bytes)
+#define nbl_centroidal_forward NBL_V(nbl_centroidal_forward)
+#define nbl_centroidal_backward NBL_V(nbl_centroidal_backward)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

@@ -27,6 +27,7 @@
 #include "inertia_backward.hip"
 #include "kinematics.hip"
 #include "dynamics.hip"
+#include "centroidal.hip"
 #include "ik.hip"
 #include "contact_readout.hip"
 
@@ -45,11 +46,12 @@ int fail(int code, const std::string& msg) {
   } while (0)
 
 constexpr int NBL_MAX_SLICES = 8;
-enum KernelId { K_FWD = 0, K_DETECT, K_BWD, K_RECOMPUTE, K_BWD_FINAL, K_SOLVE_COOP, K_BWD_A_COOP, K_ROWS_COOP, K_BWD_B_COOP, K_FWD_COOP, K_RECOMPUTE_COOP, K_BWD_FINAL_COOP, K_TREE_TO_LANES, K_CASCADE_COOP, K_CASCADE_FINAL, K_BWD_BOUNCE, K_CASCADE_FUSED, K_FWD_DETECT, K_COUNT };
+enum KernelId { K_FWD = 0, K_DETECT, K_BWD, K_RECOMPUTE, K_BWD_FINAL, K_SOLVE_COOP, K_BWD_A_COOP, K_ROWS_COOP, K_BWD_B_COOP, K_FWD_COOP, K_RECOMPUTE_COOP, K_BWD_FINAL_COOP, K_TREE_TO_LANES, K_CASCADE_COOP, K_CASCADE_FINAL, K_BWD_BOUNCE, K_CASCADE_FUSED, K_FWD_DETECT, K_CENTROIDAL, K_CENTROIDAL_VJP, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_step_forward", "k_contact_detect",
                                            "k_step_backward", "k_bwd_recompute",
                                            "k_bwd_final", "k_contact_solve_coop", "k_bwd_contact_a_coop", "k_contact_rows_coop", "k_bwd_contact_b_coop", "k_step_forward_coop", "k_bwd_recompute_coop",
-                                           "k_bwd_final_coop", "k_tree_to_lanes", "k_contact_cascade_stages", "k_contact_cascade_final", "k_bwd_bounce", "k_contact_cascade_fused", "k_forward_detect_coop"};
+                                           "k_bwd_final_coop", "k_tree_to_lanes", "k_contact_cascade_stages", "k_contact_cascade_final", "k_bwd_bounce", "k_contact_cascade_fused", "k_forward_detect_coop",
+                                           "k_centroidal", "k_centroidal_vjp"};
 struct TimedLaunch {
   hipEvent_t start, stop;
   int kernel;
@@ -1607,6 +1609,11 @@ int32_t nbl_get_timing(nbl_model* m, double* fwd_ms_sum, int64_t* fwd_count, dou
     HIP_TRY(hipEventElapsedTime(&ms, t.start, t.stop));
     m->kMs[t.kernel] += ms;
     m->kCount[t.kernel]++;
+    if (t.kernel == K_CENTROIDAL || t.kernel == K_CENTROIDAL_VJP) {   // not part of a step: per-kernel sums only
+      hipEventDestroy(t.start);
+      hipEventDestroy(t.stop);
+      continue;
+    }
     const bool isBwd = t.kernel == K_BWD || t.kernel == K_RECOMPUTE || t.kernel == K_BWD_FINAL ||
                        t.kernel == K_BWD_A_COOP || t.kernel == K_BWD_B_COOP || t.kernel == K_RECOMPUTE_COOP || t.kernel == K_BWD_FINAL_COOP || t.kernel == K_TREE_TO_LANES;
     if (isBwd) { m->bwdMs += ms; if (t.kernel == K_BWD || t.kernel == K_BWD_FINAL || t.kernel == K_BWD_FINAL_COOP) m->bwdCount++; }
@@ -2146,6 +2153,130 @@ int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, in
   }
   hipLaunchKernelGGL(k_contact_body_wrenches, dim3((unsigned)((B + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, (hipStream_t)stream,
                      (const DevBody*)m->dBodies, (const DevContactModel*)m->dContact, ent, (int)E, m->lay, m->mdl.dt, B, (const double*)saved, wrench);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// ---- centre of mass, momentum and energy of a body set (csrc/centroidal.hip) -----------------------------------------------------------------
+struct nbl_body_set {
+  int device = 0, n = 0, nb = 0;   // the model it was made for
+  DevBodySet set{};
+};
+
+int32_t nbl_body_set_create(nbl_model* m, int32_t count, const int32_t* bodies, nbl_body_set** out) {
+  if (!m || !out) return fail(NBL_E_BADARG, "null argument");
+  *out = nullptr;
+  if (count < 0 || (count > 0 && !bodies)) return fail(NBL_E_BADARG, "a body set needs `count` body indices (or none: every body)");
+  if (m->nb > CEN_MAX_BODIES)
+    return fail(NBL_E_UNSUPPORTED, "body sets are masks over at most " + std::to_string(CEN_MAX_BODIES) + " internal bodies; the model has " + std::to_string(m->nb));
+  DevBodySet set{};
+  auto add = [&](int body) {
+    int i = m->deviceBody(body);
+    set.mass |= 1ull << i;
+    set.joints |= 1ull << i;
+    // the whole chain of a ball joint / a free joint below the root: its coordinates sit on the bodies before the one that carries T_cj
+    while ((m->hBodies[i].jtype == JT_BALL || m->hBodies[i].jtype == JT_FREEC) && m->hBodies[i].ballComp > 0) {
+      i = m->hBodies[i].parent;
+      set.joints |= 1ull << i;
+    }
+  };
+  if (count == 0) {
+    for (int i = 0; i < m->userBodies; i++) add(i);
+  } else {
+    for (int k = 0; k < count; k++) {
+      if (bodies[k] < 0 || bodies[k] >= m->userBodies)
+        return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": body " + std::to_string(bodies[k]) + " out of range [0, " + std::to_string(m->userBodies) + ")");
+      for (int f = 0; f < k; f++)
+        if (bodies[f] == bodies[k]) return fail(NBL_E_BADARG, "body " + std::to_string(bodies[k]) + " is named twice (entries " + std::to_string(f) + " and " + std::to_string(k) + ")");
+      add(bodies[k]);
+    }
+  }
+  if (!(cenTotalMass(m->hBodies.data(), m->nb, set.mass) > 0.0)) return fail(NBL_E_BADARG, "the body set has no mass");
+  nbl_body_set* s = new nbl_body_set();
+  s->device = m->device; s->n = m->n; s->nb = m->nb; s->set = set;
+  *out = s;
+  return NBL_OK;
+}
+
+void nbl_body_set_destroy(nbl_body_set* s) { delete s; }
+
+int32_t nbl_body_set_origin_moments(nbl_model* m, nbl_body_set* s, int32_t count, const int32_t* bodies, const double* moments) {
+  if (!m || !s || count < 0 || (count > 0 && (!bodies || !moments))) return fail(NBL_E_BADARG, "null argument");
+  if (s->n != m->n || s->nb != m->nb || s->device != m->device) return fail(NBL_E_BADARG, "the body set was made for another model");
+  for (int k = 0; k < count; k++) {
+    if (bodies[k] < 0 || bodies[k] >= m->userBodies) return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": body out of range");
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(moments[3 * k + c])) return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": non-finite moment");
+  }
+  for (int k = 0; k < count; k++)
+    for (int c = 0; c < 3; c++) s->set.originMoment[3 * m->deviceBody(bodies[k]) + c] = moments[3 * k + c];
+  return NBL_OK;
+}
+
+double nbl_body_set_mass(nbl_model* m, const nbl_body_set* s) {
+  if (!m || !s) { (void)fail(NBL_E_BADARG, "null argument"); return 0.0; }
+  if (s->n != m->n || s->nb != m->nb || s->device != m->device) { (void)fail(NBL_E_BADARG, "the body set was made for another model"); return 0.0; }
+  return cenTotalMass(m->hBodies.data(), m->nb, s->set.mass);
+}
+
+size_t nbl_centroidal_workspace_bytes(const nbl_model* m, int64_t B) {
+  if (!m || B <= 0) return 0;
+  return sizeof(double) * (size_t)m->nb * CEN_SLOTS * (size_t)B;
+}
+
+static int32_t cenCheck(const nbl_model* m, const nbl_body_set* s, int64_t B, const double* state, int32_t flags, const void* workspace,
+                        size_t workspace_bytes) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (!s) return fail(NBL_E_BADARG, "null body set");
+  if (s->n != m->n || s->nb != m->nb || s->device != m->device) return fail(NBL_E_BADARG, "the body set was made for another model");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (flags & ~CEN_FLAG_MASK) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~CEN_FLAG_MASK) + " (NBL_CEN_*)");
+  if (B == 0) return NBL_OK;
+  if (!state) return fail(NBL_E_BADARG, "null argument");
+  if ((B + CEN_BLOCK - 1) / CEN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  if (!(cenTotalMass(m->hBodies.data(), m->nb, s->set.mass) > 0.0)) return fail(NBL_E_BADARG, "the body set has no mass");
+  const size_t need = nbl_centroidal_workspace_bytes(m, B);
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "centroidal workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_centroidal_workspace_bytes() = " + std::to_string(need));
+  return NBL_OK;
+}
+
+int32_t nbl_centroidal_forward(nbl_model* m, const nbl_body_set* set, int64_t B, const double* state, const double* accel, int32_t flags,
+                               double* com, double* com_vel, double* com_acc, double* momentum, double* ke, double* pe, double* Jcom,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = cenCheck(m, set, B, state, flags, workspace, workspace_bytes);
+  if (rc != NBL_OK) return rc;
+  if (com_acc && !accel) return fail(NBL_E_BADARG, "com_acc needs the accelerations (accel is null)");
+  if (B == 0 || !(com || com_vel || com_acc || momentum || ke || pe || Jcom)) return NBL_OK;
+  DeviceGuard guard(m->device);
+  hipStream_t s = (hipStream_t)stream;
+  m->timingNow = m->timing;
+  TIMED(K_CENTROIDAL, hipLaunchKernelGGL(k_centroidal, dim3((unsigned)((B + CEN_BLOCK - 1) / CEN_BLOCK)), dim3(CEN_BLOCK), 0, s,
+                                         (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, set->set, (int)flags, B, state, accel, com,
+                                         com_vel, com_acc, momentum, ke, pe, Jcom, (double*)workspace));
+  m->timingNow = false;
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* set, int64_t B, const double* state, const double* accel, int32_t flags,
+                                const double* g_com, const double* g_com_vel, const double* g_com_acc, const double* g_momentum,
+                                const double* g_ke, const double* g_pe, double* grad_state, double* grad_accel, int32_t accumulate,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = cenCheck(m, set, B, state, flags, workspace, workspace_bytes);
+  if (rc != NBL_OK) return rc;
+  if (g_com_acc && !accel) return fail(NBL_E_BADARG, "g_com_acc needs the accelerations (accel is null)");
+  if (B == 0 || (!grad_state && !grad_accel)) return NBL_OK;
+  DeviceGuard guard(m->device);
+  hipStream_t s = (hipStream_t)stream;
+  m->timingNow = m->timing;
+  TIMED(K_CENTROIDAL_VJP, hipLaunchKernelGGL(k_centroidal_vjp, dim3((unsigned)((B + CEN_BLOCK - 1) / CEN_BLOCK)), dim3(CEN_BLOCK), 0, s,
+                                             (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, set->set, (int)flags, B, state, accel,
+                                             g_com, g_com_vel, g_com_acc, g_momentum, g_ke, g_pe, grad_state, grad_accel, accumulate ? 1 : 0,
+                                             (double*)workspace));
+  m->timingNow = false;
   HIP_TRY(hipGetLastError());
   return NBL_OK;
 }

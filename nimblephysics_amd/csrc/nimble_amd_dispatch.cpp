@@ -97,7 +97,17 @@
                                           double*, double*, void*, size_t, void*);                                                            \
   int32_t nbl_contact_readout##S(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);                              \
   int32_t nbl_contact_readout_rows##S(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);                                   \
-  int32_t nbl_contact_body_wrenches##S(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);
+  int32_t nbl_contact_body_wrenches##S(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);                              \
+  int32_t nbl_body_set_create##S(void*, int32_t, const int32_t*, void**);                                                                  \
+  void nbl_body_set_destroy##S(void*);                                                                                                     \
+  double nbl_body_set_mass##S(void*, const void*);                                                                                         \
+  int32_t nbl_body_set_origin_moments##S(void*, void*, int32_t, const int32_t*, const double*);                                            \
+  size_t nbl_centroidal_workspace_bytes##S(const void*, int64_t);                                                                          \
+  int32_t nbl_centroidal_forward##S(void*, const void*, int64_t, const double*, const double*, int32_t, double*, double*, double*, double*, \
+                                    double*, double*, double*, void*, size_t, void*);                                                      \
+  int32_t nbl_centroidal_backward##S(void*, const void*, int64_t, const double*, const double*, int32_t, const double*, const double*,     \
+                                     const double*, const double*, const double*, const double*, double*, double*, int32_t, void*, size_t, \
+                                     void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -173,6 +183,13 @@ struct Variant {
   int32_t (*contact_readout)(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);
   int32_t (*contact_readout_rows)(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);
   int32_t (*contact_body_wrenches)(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);
+  int32_t (*body_set_create)(void*, int32_t, const int32_t*, void**);
+  void (*body_set_destroy)(void*);
+  double (*body_set_mass)(void*, const void*);
+  int32_t (*body_set_origin_moments)(void*, void*, int32_t, const int32_t*, const double*);
+  size_t (*centroidal_workspace_bytes)(const void*, int64_t);
+  int32_t (*centroidal_forward)(void*, const void*, int64_t, const double*, const double*, int32_t, double*, double*, double*, double*, double*, double*, double*, void*, size_t, void*);
+  int32_t (*centroidal_backward)(void*, const void*, int64_t, const double*, const double*, int32_t, const double*, const double*, const double*, const double*, const double*, const double*, double*, double*, int32_t, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -188,7 +205,9 @@ struct Variant {
    nbl_forward_dynamics_workspace_bytes##S, nbl_forward_dynamics_forward##S, nbl_forward_dynamics_backward##S, nbl_inv_mass_apply##S,       \
    nbl_inv_mass_matrix##S, nbl_wrench_workspace_bytes##S, nbl_inverse_dynamics_wrench_forward##S,                                          \
    nbl_inverse_dynamics_wrench_backward##S, nbl_forward_dynamics_wrench_forward##S, nbl_forward_dynamics_wrench_backward##S,                \
-   nbl_contact_inverse_dynamics##S, nbl_contact_readout##S, nbl_contact_readout_rows##S, nbl_contact_body_wrenches##S}
+   nbl_contact_inverse_dynamics##S, nbl_contact_readout##S, nbl_contact_readout_rows##S, nbl_contact_body_wrenches##S,       \
+   nbl_body_set_create##S, nbl_body_set_destroy##S, nbl_body_set_mass##S, nbl_body_set_origin_moments##S,         \
+   nbl_centroidal_workspace_bytes##S, nbl_centroidal_forward##S, nbl_centroidal_backward##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -198,6 +217,10 @@ struct nbl_model {
   void* impl;
 };
 struct nbl_kin_map {
+  const Variant* v;   // the instantiation of the model it was made against
+  void* impl;
+};
+struct nbl_body_set {
   const Variant* v;   // the instantiation of the model it was made against
   void* impl;
 };
@@ -488,6 +511,50 @@ int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int
 }
 int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream) {
   return NBL_FWD(m, contact_body_wrenches, B, saved, E, bodies, wrench, stream);
+}
+
+int32_t nbl_body_set_create(nbl_model* m, int32_t count, const int32_t* bodies, nbl_body_set** out) {
+  if (!m || !out) return ownError(NBL_E_BADARG, "null argument");
+  *out = nullptr;
+  void* impl = nullptr;
+  const int32_t rc = noted(m, m->v->body_set_create(m->impl, count, bodies, &impl));
+  if (rc != NBL_OK) return rc;
+  *out = new nbl_body_set{m->v, impl};
+  return NBL_OK;
+}
+void nbl_body_set_destroy(nbl_body_set* s) {
+  if (!s) return;
+  s->v->body_set_destroy(s->impl);
+  delete s;
+}
+double nbl_body_set_mass(nbl_model* m, const nbl_body_set* s) {
+  if (!m || !s) { (void)ownError(NBL_E_BADARG, "null argument"); return 0.0; }
+  if (s->v != m->v) { (void)ownError(NBL_E_BADARG, "the body set was made for another model"); return 0.0; }
+  g_errVariant = m->v;   // (a refusal's text is the instantiation's)
+  return m->v->body_set_mass(m->impl, s->impl);
+}
+int32_t nbl_body_set_origin_moments(nbl_model* m, nbl_body_set* s, int32_t count, const int32_t* bodies, const double* moments) {
+  if (!s) return ownError(NBL_E_BADARG, "null body set");
+  if (m && s->v != m->v) return ownError(NBL_E_BADARG, "the body set was made for another model");
+  return NBL_FWD(m, body_set_origin_moments, s->impl, count, bodies, moments);
+}
+size_t nbl_centroidal_workspace_bytes(const nbl_model* m, int64_t B) { return m ? m->v->centroidal_workspace_bytes(m->impl, B) : 0; }
+int32_t nbl_centroidal_forward(nbl_model* m, const nbl_body_set* s, int64_t B, const double* state, const double* accel, int32_t flags,
+                               double* com, double* com_vel, double* com_acc, double* momentum, double* ke, double* pe, double* Jcom,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (!s) return ownError(NBL_E_BADARG, "null body set");
+  if (m && s->v != m->v) return ownError(NBL_E_BADARG, "the body set was made for another model");
+  return NBL_FWD(m, centroidal_forward, s->impl, B, state, accel, flags, com, com_vel, com_acc, momentum, ke, pe, Jcom, workspace, workspace_bytes,
+                 stream);
+}
+int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* s, int64_t B, const double* state, const double* accel, int32_t flags,
+                                const double* g_com, const double* g_com_vel, const double* g_com_acc, const double* g_momentum,
+                                const double* g_ke, const double* g_pe, double* grad_state, double* grad_accel, int32_t accumulate,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (!s) return ownError(NBL_E_BADARG, "null body set");
+  if (m && s->v != m->v) return ownError(NBL_E_BADARG, "the body set was made for another model");
+  return NBL_FWD(m, centroidal_backward, s->impl, B, state, accel, flags, g_com, g_com_vel, g_com_acc, g_momentum, g_ke, g_pe, grad_state,
+                 grad_accel, accumulate, workspace, workspace_bytes, stream);
 }
 
 void nbl_ik_default_config(nbl_ik_config* c) { nbl_ik_default_config_c8(c); }   // (the same in every instantiation)

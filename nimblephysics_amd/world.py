@@ -397,6 +397,46 @@ class World:
         from .dynamics import world_inverse_dynamics_from_predictions
         return world_inverse_dynamics_from_predictions(self, accelerations, bodies, root_frame_wrenches, root_residuals)
 
+    # ---- centre of mass, momentum and energy of the current state (centroidal.py; Skeleton.cpp:11310, 13598-13790) ----
+    # `skeleton`: an id of description.body_skeletons() (None: every body that is not fixed to the world).  Detached, like getMassMatrix;
+    # [B, ...] on the World's device ([...] when the state was set as one 1-D vector).  The state is left untouched.
+    def getMass(self, skeleton=None) -> float:
+        """Skeleton::getMass at the current inertias (World.setMasses moves it)."""
+        from .centroidal import total_mass
+        return total_mass(self, None, skeleton)
+
+    def getCOM(self, skeleton=None) -> torch.Tensor:
+        """Skeleton::getCOM in world coordinates: [B, 3]."""
+        from .centroidal import world_centroidal
+        return world_centroidal(self, 0, skeleton)
+
+    def getCOMLinearVelocity(self, skeleton=None) -> torch.Tensor:
+        """Skeleton::getCOMLinearVelocity(World, World): [B, 3]."""
+        from .centroidal import world_centroidal
+        return world_centroidal(self, 1, skeleton)
+
+    def getCOMLinearAcceleration(self, accelerations, skeleton=None) -> torch.Tensor:
+        """Skeleton::getCOMLinearAcceleration at the joint accelerations [B, n] ([n]): [B, 3], gravity not included."""
+        from .centroidal import world_centroidal
+        return world_centroidal(self, 2, skeleton, accelerations)
+
+    def getCOMLinearJacobian(self, skeleton=None) -> torch.Tensor:
+        """Skeleton::getCOMLinearJacobian in world coordinates: [B, 3, n] over the device's (mobile) coordinates."""
+        from .centroidal import world_centroidal
+        return world_centroidal(self, 6, skeleton)
+
+    def computeKineticEnergy(self, skeleton=None) -> torch.Tensor:
+        """Skeleton::computeKineticEnergy: [B]."""
+        from .centroidal import world_centroidal
+        return world_centroidal(self, 4, skeleton)
+
+    def computePotentialEnergy(self, skeleton=None) -> torch.Tensor:
+        """Skeleton::computePotentialEnergy: [B].  THE REFERENCE'S RULE: gravity acts at the ORIGIN of every body's frame, not at its
+        centre of mass (BodyNode::computePotentialEnergy, BodyNode.cpp:2372-2375), plus the joint spring energy.  The energy with gravity
+        at the centres of mass - the one whose gradient is the gravity force - is centroidal.potential_energy(at_com=True)."""
+        from .centroidal import CEN_PE_BODY_ORIGIN, world_centroidal
+        return world_centroidal(self, 5, skeleton, flags=CEN_PE_BODY_ORIGIN)
+
     def reset_lcp_cache(self):
         self.lcp_cache = None
 
@@ -469,6 +509,7 @@ class World:
         if isinstance(masses, torch.Tensor):
             masses = masses.detach().cpu().numpy()
         self._wrt_mass.set(np.asarray(masses, dtype=np.float64))
+        self._mass_version = getattr(self, "_mass_version", 0) + 1     # (centroidal.py: the origin moments of weld-merged bodies follow the masses)
         new = self.description.merge_welds() if self.description.has_welds() else self.description
         changed, values = [], {}
         for i, new_b in enumerate(new.bodies):
