@@ -419,6 +419,17 @@ int32_t nbl_selftest_pinv(int32_t count, const double* Q, const int32_t* cTrue, 
 /* The same on rows x rows matrices, rows = 24 or 48: the pseudo-inverses of the 24-row and of the 48-row instantiation of the contact stage. */
 int32_t nbl_selftest_pinv_rows(int32_t count, int32_t rows, const double* Q, const int32_t* cTrue, int32_t route, double* P, int32_t* rank,
                                int32_t reps, double* ms_per_launch);
+/* Stage 0 of the LCP cascade and its standardisation loop (coopStage0 / coopStandardizeLoop: classify, build Q, pseudo-inverse, apply,
+ * isLCPSolutionValid) on `count` caller-supplied contact LCPs (HOST pointers), one wavefront per problem, rows = 24 or 48: A [count][rows*rows]
+ * row-major, b and x_cache [count][rows], mu [count][rows / 3]; per problem the 64-bit words mask (the rows of the constrained group at
+ * hand; the problem's size is the whole contacts up to its last bit), lim_mask (joint-limit rows) and neg_mask (the ones carried negated);
+ * cfm [count]: 0 = stage 0 (have_cache [count]: start from x_cache instead of the guess), otherwise the standardisation loop alone on
+ * x_cache with that constant on the diagonal, as after stages 2 / 3.  Outputs x, x0 (the pre-solve x), cls (0 / 1 / 2), e_out (the +-mu of
+ * an upper-bound row) [count][rows], ok [count] (bit 0: standardised valid solution, bit 1: pinv is Q^+ of the final classification) and
+ * pinv [count][rows*rows] (zero without bit 1).  For tests (tests/test_gpu_stage0_selftest.py); added within minor 5. */
+int32_t nbl_selftest_stage0_rows(int32_t count, int32_t rows, const double* A, const double* b, const double* mu, const uint64_t* mask,
+                                 const uint64_t* lim_mask, const uint64_t* neg_mask, const double* cfm, const int32_t* have_cache,
+                                 const double* x_cache, double* x, double* x0, int32_t* cls, double* e_out, int32_t* ok, double* pinv);
 
 /*
  * Layout helpers: the Python surface takes world-major tensors [B][d] like a stack of the

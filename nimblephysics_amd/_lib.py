@@ -112,6 +112,8 @@ def lib():
     L.nbl_selftest_pinv.restype = C.c_int32
     L.nbl_selftest_pinv_rows.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp]
     L.nbl_selftest_pinv_rows.restype = C.c_int32
+    L.nbl_selftest_stage0_rows.argtypes = [C.c_int32, C.c_int32] + [vp] * 15
+    L.nbl_selftest_stage0_rows.restype = C.c_int32
     L.nbl_kin_map_create.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(vp)]
     L.nbl_kin_map_create.restype = C.c_int32
     L.nbl_kin_map_destroy.argtypes = [vp]
@@ -187,7 +189,7 @@ EXPORTED_SYMBOLS = [
     "nbl_set_body_inertia", "nbl_set_body_inertias", "nbl_set_inertia_params", "nbl_set_inertia_params_on", "nbl_num_inertia_params", "nbl_backward_inertia", "nbl_rollout_backward_inertia",
     "nbl_rollout_checkpoint_bytes", "nbl_rollout_forward_checkpointed", "nbl_rollout_backward_checkpointed",
     "nbl_get_timing", "nbl_kernel_count", "nbl_kernel_name", "nbl_kernel_timing", "nbl_selftest_lcp_dantzig", "nbl_selftest_lcp_dantzig_timed", "nbl_selftest_lcp_cascade", "nbl_selftest_pinv",
-    "nbl_model_max_contacts", "nbl_selftest_pinv_rows",
+    "nbl_model_max_contacts", "nbl_selftest_pinv_rows", "nbl_selftest_stage0_rows",
     "nbl_kin_map_create", "nbl_kin_map_destroy", "nbl_kin_map_dim", "nbl_kinematics_forward", "nbl_kinematics_backward",
     "nbl_dynamics_workspace_bytes", "nbl_inverse_dynamics_forward", "nbl_inverse_dynamics_backward", "nbl_mass_matrix",
     "nbl_forward_dynamics_workspace_bytes", "nbl_forward_dynamics_forward", "nbl_forward_dynamics_backward", "nbl_inv_mass_apply", "nbl_inv_mass_matrix",

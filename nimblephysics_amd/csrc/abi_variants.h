@@ -50,6 +50,7 @@
 #define nbl_selftest_lcp_cascade NBL_V(nbl_selftest_lcp_cascade)
 #define nbl_selftest_pinv NBL_V(nbl_selftest_pinv)
 #define nbl_selftest_pinv_rows NBL_V(nbl_selftest_pinv_rows)
+#define nbl_selftest_stage0_rows NBL_V(nbl_selftest_stage0_rows)
 #define nbl_set_body_inertia NBL_V(nbl_set_body_inertia)
 #define nbl_set_body_inertias NBL_V(nbl_set_body_inertias)
 #define nbl_set_inertia_params NBL_V(nbl_set_inertia_params)

@@ -783,6 +783,23 @@ struct CoopRow {
   DEV double a(const double* p, int i) const { return (on && i < m) ? p[i * MAXR] : 0.0; }
 };
 
+// The part of a row's set-up that does not depend on where the row comes from (coopLoadRow of coop_kernels.hip: the saved record;
+// k_selftest_stage0: caller-supplied problems): which lane carries what, and the squared norm of the lane's column of A (R.m, R.on and
+// R.Acol set by the caller).
+DEV void coopRowShape(CoopRow& R, int ln) {
+  R.fric = (ln % 3) != 0;
+  R.fp = ln < MAXR ? ln - (ln % 3) : 0;
+}
+DEV double coopColNorm(const CoopRow& R) {
+  double cn = 0.0, cn1 = 0.0;
+#pragma unroll 1
+  for (int ib = 0; ib < MAXR; ib += 8) {
+#pragma unroll
+    for (int iq = 0; iq < 8; iq += 2) { const double x = R.a(ib + iq), y = R.a(ib + iq + 1); cn = fma(x, x, cn); cn1 = fma(y, y, cn1); }
+  }
+  return cn + cn1;
+}
+
 // A x for this lane's row, x one entry per lane; vec: MAXR doubles of LDS scratch
 template <class W>
 DEV double coopAx(const W& w, double* vec, const CoopRow& R, double xLane) {

@@ -25,8 +25,7 @@ template <bool LIM = false>
 DEV void coopLoadRow(CoopRow& R, int ln, int m, const double* __restrict__ saved, const double* __restrict__ dn,
                      const SavedLayout& lay, const DevContactModel* __restrict__ cm, int64_t B, int64_t b) {
   R.m = m;
-  R.fric = (ln % 3) != 0;
-  R.fp = ln < MAXR ? ln - (ln % 3) : 0;
+  coopRowShape(R, ln);
   R.mu = 0.0; R.Bv = 0.0;
   const bool on = ln < m;
   if (on) {
@@ -41,13 +40,7 @@ DEV void coopLoadRow(CoopRow& R, int ln, int m, const double* __restrict__ saved
   R.on = on;
   if (LIM) R.limMask = (RowMask)__ballot(R.lim ? 1 : 0);
   R.Acol = dn + lay.A + (on ? ln : 0);
-  double cn = 0.0, cn1 = 0.0;
-#pragma unroll 1
-  for (int ib = 0; ib < MAXR; ib += 8) {
-#pragma unroll
-    for (int iq = 0; iq < 8; iq += 2) { const double x = R.a(ib + iq), y = R.a(ib + iq + 1); cn = fma(x, x, cn); cn1 = fma(y, y, cn1); }
-  }
-  R.colNorm = cn + cn1;
+  R.colNorm = coopColNorm(R);
 }
 
 // Constrained groups of a world's contacts (ConstraintSolver::buildConstrainedGroups :724-780, ContactConstraint::uniteSkeletons
@@ -561,6 +554,58 @@ __global__ __launch_bounds__(64) void k_selftest_pinv(int count, const double* _
     for (int i = 0; i < MAXR; i++) P[pb * MAXR * MAXR + i * MAXR + ln] = S.P[i * CLD + ln];
   }
   if (ln == 0) rank[pb] = r;
+}
+
+// Self-test of stage 0 and of the standardisation loop (nbl_selftest_stage0_rows): one wavefront per problem, the row set up with coopLoadRow's
+// own helpers (coopRowShape, coopColNorm; m = the rows up to the last one of `mask`, whole contacts; the column norm over all of them), then the rows outside `mask` switched
+// off like the rows of a world's other constrained groups, and the joint-limit rows marked as the general instantiation marks them.
+// cfm = 0: coopStage0 (guess or warm start, then the loop); cfm != 0: the loop alone on xcache with that constant on the diagonal, as the
+// cascade kernels call it after stages 2 / 3.  Exactly the device code of k_contact_solve_coop / k_contact_cascade_final.
+__global__ __launch_bounds__(64) void k_selftest_stage0(int count, const double* __restrict__ A, const double* __restrict__ b, const double* __restrict__ mu,
+                                                       const uint64_t* __restrict__ mask, const uint64_t* __restrict__ limMask,
+                                                       const uint64_t* __restrict__ negMask, const double* __restrict__ cfm,
+                                                       const int32_t* __restrict__ haveCache, const double* __restrict__ xcache,
+                                                       double* __restrict__ X, double* __restrict__ X0, int32_t* __restrict__ cls,
+                                                       double* __restrict__ E, int32_t* __restrict__ ok, double* __restrict__ P) {
+  __shared__ CoopLds S;
+  const DevWave w;
+  const int ln = w.lane();
+  const int64_t pb = blockIdx.x;
+  if (pb >= count) return;
+  const uint64_t mk = mask[pb], lm = limMask[pb], ng = negMask[pb];
+  const int top = 64 - __builtin_clzll(mk | 1ull);
+  const int m3 = 3 * ((top + 2) / 3);
+  const int m = m3 < MAXR ? m3 : MAXR;
+  CoopRow R;
+  R.m = m;
+  coopRowShape(R, ln);
+  R.on = ln < m;
+  R.mu = R.on ? mu[pb * (MAXR / 3) + ln / 3] : 0.0;
+  R.Bv = R.on ? b[pb * MAXR + ln] : 0.0;
+  R.Acol = A + pb * MAXR * MAXR + (R.on ? ln : 0);
+  R.colNorm = coopColNorm(R);
+  R.on = R.on && ((mk >> ln) & 1ull);
+  R.lim = ln < m && ((lm >> ln) & 1ull);
+  R.neg = ln < m && ((ng >> ln) & 1ull);
+  R.limMask = (RowMask)lm;
+  const double xc = ln < m ? xcache[pb * MAXR + ln] : 0.0;
+  const double c = cfm[pb];
+  CoopStage0 out;
+  if (c == 0.0) coopStage0(w, S, R, haveCache[pb] != 0, xc, out);
+  else {
+    double x = R.on ? xc : 0.0;
+    bool pinvValid = false;
+    out.X0 = x;
+    out.ok = coopStandardizeLoop(w, S, R, x, c, false, (RowMask)0, pinvValid, out.K);
+    out.X = x;
+    out.pinvValid = out.ok && pinvValid;
+  }
+  if (ln < MAXR) {
+    X[pb * MAXR + ln] = out.X; X0[pb * MAXR + ln] = out.X0; cls[pb * MAXR + ln] = out.K.cls; E[pb * MAXR + ln] = out.K.E;
+#pragma unroll 1
+    for (int i = 0; i < MAXR; i++) P[pb * MAXR * MAXR + i * MAXR + ln] = out.pinvValid ? S.P[i * CLD + ln] : 0.0;
+  }
+  if (ln == 0) ok[pb] = (out.ok ? 1 : 0) | (out.pinvValid ? 2 : 0);
 }
 
 // Dense part of the contact adjoint, one world per wavefront (the header of contact_backward.hip derives the

@@ -1307,6 +1307,58 @@ int32_t nbl_selftest_pinv(int32_t count, const double* Q, const int32_t* cTrue, 
 #endif
 }
 
+// ---- self-test: stage 0 / the standardisation loop on caller-supplied contact LCPs (host pointers) ----------------------------
+int32_t nbl_selftest_stage0_rows(int32_t count, int32_t rows, const double* A, const double* b, const double* mu, const uint64_t* mask,
+                                 const uint64_t* lim_mask, const uint64_t* neg_mask, const double* cfm, const int32_t* have_cache,
+                                 const double* x_cache, double* x, double* x0, int32_t* cls, double* e_out, int32_t* ok, double* pinv) {
+#if NBL_GENERAL
+  (void)count; (void)rows; (void)A; (void)b; (void)mu; (void)mask; (void)lim_mask; (void)neg_mask; (void)cfm; (void)have_cache; (void)x_cache;
+  (void)x; (void)x0; (void)cls; (void)e_out; (void)ok; (void)pinv;
+  return fail(NBL_E_UNSUPPORTED, "nbl_selftest_stage0_rows addresses the 24- and 48-row instantiations (the general one: nbl_selftest_lcp_cascade)");
+#else
+  if (rows != MAX_ROWS) return fail(NBL_E_BADARG, "rows must be " + std::to_string(MAX_ROWS) + " in this instantiation of the library");
+  if (!A || !b || !mu || !mask || !lim_mask || !neg_mask || !cfm || !have_cache || !x_cache || !x || !x0 || !cls || !e_out || !ok || !pinv)
+    return fail(NBL_E_BADARG, "null argument");
+  if (count <= 0) return fail(NBL_E_BADARG, "count must be positive");
+  if (nbl_device_count() <= 0) return fail(NBL_E_NOGPU, "no HIP device visible");
+  const size_t nv = (size_t)count * MAX_ROWS, nm = nv * MAX_ROWS, nc = (size_t)count * MAX_CONTACTS;
+  // doubles: A, pinv | b, xcache, x, x0, e | mu | cfm;  64-bit words: mask, limMask, negMask;  32-bit words: haveCache, ok | cls
+  double *dM = nullptr, *dv = nullptr;
+  uint64_t* dk = nullptr;
+  int32_t* di = nullptr;
+  hipError_t e = hipMalloc((void**)&dM, 2 * nm * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&dv, (5 * nv + nc + count) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&dk, 3 * (size_t)count * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&di, (2 * (size_t)count + nv) * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemcpy(dM, A, nm * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv, b, nv * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv + nv, x_cache, nv * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv + 5 * nv, mu, nc * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv + 5 * nv + nc, cfm, (size_t)count * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dk, mask, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dk + count, lim_mask, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dk + 2 * (size_t)count, neg_mask, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(di, have_cache, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_selftest_stage0, dim3((unsigned)count), dim3(64), 0, 0, count, dM, dv, dv + 5 * nv, dk, dk + count, dk + 2 * (size_t)count,
+                       dv + 5 * nv + nc, di, dv + nv, dv + 2 * nv, dv + 3 * nv, di + 2 * (size_t)count, dv + 4 * nv, di + count, dM + nm);
+    e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(x, dv + 2 * nv, nv * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(x0, dv + 3 * nv, nv * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(e_out, dv + 4 * nv, nv * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(cls, di + 2 * (size_t)count, nv * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ok, di + count, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(pinv, dM + nm, nm * sizeof(double), hipMemcpyDeviceToHost);
+  if (dM) hipFree(dM);
+  if (dv) hipFree(dv);
+  if (dk) hipFree(dk);
+  if (di) hipFree(di);
+  if (e != hipSuccess) return fail(NBL_E_HIP, std::string("nbl_selftest_stage0_rows: ") + hipGetErrorString(e));
+  return NBL_OK;
+#endif
+}
+
 #ifdef NBL_CASCADE_TIMING
 int32_t nbl_debug_dantzig_stats(unsigned long long* out16, int32_t reset) {
   HIP_TRY(hipDeviceSynchronize());

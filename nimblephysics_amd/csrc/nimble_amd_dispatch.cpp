@@ -48,6 +48,9 @@
   int32_t nbl_selftest_lcp_dantzig_timed##S(int32_t, int32_t, const double*, const double*, const double*, const double*, const int32_t*,  \
                                             double*, int32_t*, int32_t, double*);                                                          \
   int32_t nbl_selftest_pinv_rows##S(int32_t, int32_t, const double*, const int32_t*, int32_t, double*, int32_t*, int32_t, double*);        \
+  int32_t nbl_selftest_stage0_rows##S(int32_t, int32_t, const double*, const double*, const double*, const uint64_t*, const uint64_t*,     \
+                                      const uint64_t*, const double*, const int32_t*, const double*, double*, double*, int32_t*, double*,  \
+                                      int32_t*, double*);                                                                                  \
   int32_t nbl_selftest_lcp_cascade##S(int32_t, int32_t, const double*, const double*, const double*, int32_t, const double*, const uint8_t*, double,   \
                                       double*, int32_t*, uint32_t*, double*);                                                              \
   int32_t nbl_transpose_to_soa##S(const double*, double*, int64_t, int32_t, void*);                                                        \
@@ -373,6 +376,14 @@ int32_t nbl_selftest_pinv_rows(int32_t count, int32_t rows, const double* Q, con
 int32_t nbl_selftest_pinv(int32_t count, const double* Q, const int32_t* cTrue, int32_t route, double* P, int32_t* rank, int32_t reps,
                           double* ms_per_launch) {
   return nbl_selftest_pinv_rows(count, 24, Q, cTrue, route, P, rank, reps, ms_per_launch);
+}
+int32_t nbl_selftest_stage0_rows(int32_t count, int32_t rows, const double* A, const double* b, const double* mu, const uint64_t* mask,
+                                 const uint64_t* lim_mask, const uint64_t* neg_mask, const double* cfm, const int32_t* have_cache,
+                                 const double* x_cache, double* x, double* x0, int32_t* cls, double* e_out, int32_t* ok, double* pinv) {
+  if (rows != 24 && rows != 48) return ownError(NBL_E_BADARG, "rows must be 24 or 48");
+  g_errVariant = &kVariants[rows == 48 ? 1 : 0];
+  return rows == 48 ? nbl_selftest_stage0_rows_c16(count, rows, A, b, mu, mask, lim_mask, neg_mask, cfm, have_cache, x_cache, x, x0, cls, e_out, ok, pinv)
+                    : nbl_selftest_stage0_rows_c8(count, rows, A, b, mu, mask, lim_mask, neg_mask, cfm, have_cache, x_cache, x, x0, cls, e_out, ok, pinv);
 }
 
 int32_t nbl_transpose_to_soa(const double* src_bd, double* dst_db, int64_t B, int32_t d, void* stream) {

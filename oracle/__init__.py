@@ -81,6 +81,8 @@ def _declare(lib):
     lib.nbo_last_contacts.restype = C.c_int
     lib.nbo_last_lcp.argtypes = [C.c_void_p, pd, pd, pd, pd, pd, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.nbo_last_lcp.restype = C.c_int
+    lib.nbo_last_lcp_cfm.argtypes = [C.c_void_p, pd, C.c_int]
+    lib.nbo_last_lcp_cfm.restype = C.c_int
     return lib
 
 
@@ -278,5 +280,7 @@ class OracleWorld:
         fi = np.zeros(cap, np.int32); rc = np.zeros(cap, np.int32)
         m = self._lib.nbo_last_lcp(self._h, _p(A), _p(b), _p(x), _p(lo), _p(hi), fi.ctypes.data_as(C.POINTER(C.c_int32)),
                                    rc.ctypes.data_as(C.POINTER(C.c_int32)), cap)
+        cfm = np.zeros(cap)
+        assert self._lib.nbo_last_lcp_cfm(self._h, _p(cfm), cap) == m
         return {"A": A[:m * m].reshape(m, m).copy(), "b": b[:m].copy(), "x": x[:m].copy(), "lo": lo[:m].copy(),
-                "hi": hi[:m].copy(), "findex": fi[:m].copy(), "row_class": rc[:m].copy()}
+                "hi": hi[:m].copy(), "findex": fi[:m].copy(), "row_class": rc[:m].copy(), "cfm": cfm[:m].copy()}   # (A holds cfm on its diagonal)

@@ -450,6 +450,15 @@ int nbo_last_contacts(void* h, double* out /* [C][12]: p(3) n(3) depth type body
   }
   return C;
 }
+// per LCP row of the last step: the constraint-force-mixing constant its constrained group's solver ended with (nbo_last_lcp's A holds it
+// on its diagonal); returns the number of rows
+int nbo_last_lcp_cfm(void* h, double* cfmRow, int cap) {
+  Oracle* o = (Oracle*)h;
+  const ContactResult& cr = o->snap.contact;
+  if (cr.m > cap) return -cr.m;
+  for (int i = 0; i < cr.m; i++) cfmRow[i] = i < (int)cr.cfmRow.size() ? cr.cfmRow[i] : 0.0;
+  return cr.m;
+}
 int nbo_last_lcp(void* h, double* A, double* b, double* x, double* lo, double* hi, int32_t* findex, int32_t* rowClass,
                  int cap) {
   Oracle* o = (Oracle*)h;

@@ -161,6 +161,41 @@ int shim_coop_cascade_lim(int m, const double* A, const double* b, const double*
   return (int)stOut;
 }
 
+// What k_selftest_stage0 (nbl_selftest_stage0_rows) runs on the device, on one problem: the problem's size from the last bit of `mask`, the
+// rows outside it off, joint-limit rows, cfm = 0: coopStage0, otherwise the standardisation loop alone on xcache with that cfm.
+// Returns ok | pinvValid << 1; Pout is zero without pinvValid.
+int shim_coop_stage0_rows(const double* A, const double* b, const double* mu, unsigned long long mask, unsigned long long limMask, unsigned long long negMask,
+                          double cfm, int haveCache, const double* xcache, double* X, double* X0, int* cls, double* E, double* Pout) {
+  static CoopLds S;
+  int ret = 0;
+  int top = 0;
+  for (int i = 0; i < 64; i++) if ((mask >> i) & 1ull) top = i + 1;
+  if (top == 0) top = 1;
+  const int m3 = 3 * ((top + 2) / 3), m = m3 < MAXR ? m3 : MAXR;
+  emuRunWave([&](const EmuWave& w) {
+    const int ln = w.lane();
+    CoopRow R;
+    fillRow(R, ln, m, A, b, mu);
+    R.on = R.on && ((mask >> ln) & 1ull);
+    R.lim = ln < m && ((limMask >> ln) & 1ull); R.neg = ln < m && ((negMask >> ln) & 1ull); R.limMask = (RowMask)limMask;
+    const double xc = ln < m ? xcache[ln] : 0.0;
+    CoopStage0 out;
+    if (cfm == 0.0) coopStage0(w, S, R, haveCache != 0, xc, out);
+    else {
+      double x = R.on ? xc : 0.0;
+      bool pinvValid = false;
+      out.X0 = x;
+      out.ok = coopStandardizeLoop(w, S, R, x, cfm, false, (RowMask)0, pinvValid, out.K);
+      out.X = x;
+      out.pinvValid = out.ok && pinvValid;
+    }
+    if (ln < MAXR) { X[ln] = out.X; X0[ln] = out.X0; cls[ln] = out.K.cls; E[ln] = out.K.E; }
+    if (ln == 0) ret = (out.ok ? 1 : 0) | (out.pinvValid ? 2 : 0);
+  });
+  for (int i = 0; i < MAXR; i++) for (int j = 0; j < MAXR; j++) Pout[i * MAXR + j] = (ret & 2) ? S.P[i * CLD + j] : 0.0;
+  return ret;
+}
+
 // the one-world-per-lane statement (laneStage0 of lcp_dev.hpp) on the same problem
 int shim_lane_stage0(int m, const double* A, const double* b, const double* mu, int haveCache, const double* xcache,
                      double* X, double* X0, int* cls, double* E) {

@@ -125,6 +125,20 @@ def exact_reference_near_the_singularity(ow, md, s, a, g, ref, lcp=None, lcp_len
     return out, near, fd_err
 
 
+ORACLE_WITHOUT_REFERENCE_SOLVER = 0x80000000      # oracle/contact.hpp: stage 1 could not load oracle/_ref/libodelcp_ref.so
+
+
+def assert_reference_solver_present(tag, ref):
+    """The oracle's stage 1 IS the reference's own Dantzig solver, compiled into oracle/_ref by build().  Without that library the oracle
+    treats stage 1 as failed on every world that leaves stage 0 and answers with the PGS fallback: not the reference's result, and
+    stable under perturbations - so such a world reads "the reference is stable here but the device differs" (smoke() part 1: world 84
+    with 0.265; the kinematics case: world 15).  The oracle flags those worlds; a flagged reference judges nothing."""
+    if isinstance(ref, dict) and "status" in ref:
+        flagged = np.where(np.asarray(ref["status"]).astype(np.uint32) & ORACLE_WITHOUT_REFERENCE_SOLVER)[0]
+        assert len(flagged) == 0, (tag, "the oracle ran without oracle/_ref/libodelcp_ref.so (build() makes it where the reference is present): its results on "
+                                   "the worlds that leave stage 0 are not the reference's", len(flagged), flagged[:8].tolist())
+
+
 def assert_match_or_reference_unstable(tag, ow, s, a, g, dev, ref, tol, lcp=None, lcp_len=None, n_perturb=64, closeness=0.1, ulps=1,
                                        max_unstable=None, max_by_closeness=None, fd_model=None, only=None, verbose=True):
     """dev / ref: dicts of next, grad_state, grad_action [B, .].  Worlds above `tol` must be ones where the oracle's OWN result moves by
@@ -138,6 +152,7 @@ def assert_match_or_reference_unstable(tag, ow, s, a, g, dev, ref, tol, lcp=None
     worlds took which branch and returns (unstable worlds, worlds that needed the closeness branch)."""
     for k in KEYS:
         assert np.isfinite(dev[k]).all() and np.isfinite(ref[k]).all(), (tag, k, "non-finite values", int((~np.isfinite(dev[k])).sum()), int((~np.isfinite(ref[k])).sum()))
+    assert_reference_solver_present(tag, ref)
     near = np.zeros(len(ref["next"]), dtype=bool)
     fd_err = 0.0
     if fd_model is not None:

@@ -88,3 +88,49 @@ def test_round_off_pivots_of_exactly_singular_contact_matrices_are_rejected_like
             sv = np.linalg.svd(Q[t], compute_uv=False)
             ref = np.linalg.pinv(Q[t], rcond=0.5 * sv[ranks[t] - 1] / sv[0])
             assert np.abs(P[t] - ref).max() <= 1e-9 * np.abs(ref).max(), (route, t)
+
+
+# trials of the generator per build: enough for >= 200 / >= 64 accepted matrices; every third trial draws a small clamping set, so that
+# Q has full rank (at most 12 independent rows exist on two 6-DOF bodies) and the full-rank completion of the route occurs too
+HH_TRIALS = {24: (260, 130, (0.7, 0.2, 0.1)), 48: (72, 72, (0.82, 0.12, 0.06))}
+
+
+@pytest.mark.parametrize("R", [24, 48])
+def test_device_householder_route_on_contact_matrices_with_friction_rows_on_their_bound(R):
+    """coopPinv ON THE DEVICE on the matrices it is there for (tests/test_coop_host.py has the same generator on the host build):
+    Q = A(c, c) + A(c, u) E of a standing robot, friction rows on their bound folded into their normal's column - non-symmetric, cond <= 1e8.
+    Rank exact, Q^+ within 500 cond(Q) eps of numpy's pseudo-inverse; both completions (rank = rows of the clamping set / rank below it)
+    occur; and the same matrices through the host build of the same header."""
+    from nimblephysics_amd._lib import check, lib
+    from test_coop_host import _build_shim, _p
+    from util import friction_bound_contact_matrices
+    rng = np.random.default_rng(110 + R)
+    dense, sparse, p_sparse = HH_TRIALS[R]
+    cases = list(friction_bound_contact_matrices(rng, R, dense)) + list(friction_bound_contact_matrices(rng, R, sparse, p_cls=p_sparse))
+    count = len(cases)
+    assert count >= (200 if R == 24 else 64), count
+    assert count <= 768
+    Q = np.ascontiguousarray(np.stack([c[1] for c in cases])); size = np.array([c[2] for c in cases], np.int32)
+    assert np.abs(Q - Q.transpose(0, 2, 1)).max(axis=(1, 2)).astype(bool).sum() >= count // 2       # the route's own input: not symmetric
+    vp = lambda a: C.c_void_p(a.ctypes.data)
+    P = np.zeros_like(Q); r = np.zeros(count, np.int32)
+    check(lib().nbl_selftest_pinv_rows(count, R, vp(Q), vp(size), 0, vp(P), vp(r), 1, None), "nbl_selftest_pinv_rows")
+    shim = _build_shim(R // 3)
+    full = deficient = 0
+    worst = worst_host = 0.0
+    for t, (_, Qt, ncl, k, cond) in enumerate(cases):
+        assert r[t] == k, (t, r[t], k, ncl)
+        full += int(k == ncl); deficient += int(k < ncl)
+        ref = np.linalg.pinv(Qt, rcond=0.5 / cond)
+        scale = np.abs(ref).max()
+        e = np.abs(P[t] - ref).max() / scale
+        worst = max(worst, e / (cond * 2.2e-16))
+        assert e <= 500 * cond * 2.2e-16, (t, e, cond, k, ncl)
+        Ph = np.zeros((R, R))
+        assert shim.shim_coop_pinv(_p(np.ascontiguousarray(Qt)), ncl, _p(Ph)) == k, (t, k)
+        eh = np.abs(P[t] - Ph).max() / scale
+        worst_host = max(worst_host, eh / (cond * 2.2e-16))
+        assert eh <= 500 * cond * 2.2e-16, (t, eh, cond)          # (both are within the bound of numpy's: at most twice it from each other; held to once)
+    print(f"Householder route on the device, R = {R}: {count} matrices, {full} of full rank, {deficient} rank-deficient; worst error in units of cond(Q) eps: "
+          f"against numpy {worst:.3g}, against the host build {worst_host:.3g}")
+    assert full >= 10 and deficient >= 10, (full, deficient)

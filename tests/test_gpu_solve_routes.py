@@ -25,25 +25,6 @@ CASES = {
 MAX_CONTACTS, CR_SIZE, MAX_ROWS = 8, 22, 24      # the 24-row build (csrc/model_dev.hpp)
 
 
-def _record_rows(world, saved, B):
-    """x, b, cls, pflag rows and the pinv block of the saved record (SavedLayout, csrc/model_dev.hpp / nimble_amd.hip), on the device."""
-    import torch
-    n = world.n
-    rec = saved.view(torch.float64)
-    x0 = 5 * n + 1 + MAX_CONTACTS * CR_SIZE
-    b0, cls0 = x0 + MAX_ROWS, x0 + 2 * MAX_ROWS
-    pflag0 = x0 + 4 * MAX_ROWS
-    total = pflag0 + 1 + MAX_CONTACTS
-    pinv_off = MAX_ROWS * MAX_ROWS + 2 * n * MAX_ROWS
-    dense = pinv_off + MAX_ROWS * MAX_ROWS
-    rows = rec[: total * B].view(total, B)
-    blocks = rec[total * B: total * B + B * dense].view(B, dense)
-    pflag = rows[pflag0]
-    pinv = torch.where((pflag != 0)[:, None], blocks[:, pinv_off:pinv_off + MAX_ROWS * MAX_ROWS], torch.zeros((), dtype=torch.float64, device=rec.device))
-    return {"nc": rows[5 * n], "x": rows[x0:x0 + MAX_ROWS].t(), "b": rows[b0:b0 + MAX_ROWS].t(), "cls": rows[cls0:cls0 + MAX_ROWS].t(),
-            "pflag": pflag, "pinv": pinv}       # (pinv of a world without the flag is whatever the buffer held: zeroed)
-
-
 def _route_counts(status, rec):
     """Worlds per route, counted on the device from the status words and the record.  The pseudo-inverse in the record (pflag) is that of
     the final classification: the Householder route's when a friction row sits on its bound (cls +-2), whichever kernel standardised
@@ -68,7 +49,7 @@ def device_results(name):
     import nimblephysics_amd as na
     from nimblephysics_amd.contacts import read_constraint_rows
     from nimblephysics_amd.timestep import timestep
-    from util import contact_inputs
+    from util import contact_inputs, record_rows
     c = CASES[name]
     B = c["B"]
     md, s, a = contact_inputs("atlas20", B, c["seed"], joint_noise=c["joint_noise"], vel_noise=c["vel_noise"], action_noise=c["action_noise"])
@@ -83,7 +64,7 @@ def device_results(name):
         out = timestep(world, out, at)               # the second step starts from the first one's x
     status = world.last_status.clone()
     saved = world._last_saved
-    rec = _record_rows(world, saved, B)
+    rec = record_rows(world, saved, B, MAX_CONTACTS, CR_SIZE)
     # the layout read above is the record's: its x rows are the impulses the library's own readout returns
     n_rows, imp, _ = read_constraint_rows(world, saved, B)
     assert torch.equal(n_rows.to(torch.float64), 3 * rec["nc"]) and torch.equal(imp, rec["x"])

@@ -243,3 +243,64 @@ def table_inputs(B, seed, feet=4, max_contacts=16):
     s[:, 4] = -rng.uniform(1e-4, 2e-3, B)                                 # feet 0.1 .. 2 mm in the ground
     s[:, 6:] = rng.normal(0, 0.05, (B, 6)) * np.where(rng.random((B, 1)) < 0.7, 1.0, 0.02)   # most pushed / spun, some nearly at rest
     return md, s, rng.normal(0, 0.2, (B, 6))
+
+
+# ---- the matrices the Householder route is there for (tests/test_coop_host.py, tests/test_gpu_pinv_selftest.py) ----
+def friction_bound_contact_matrices(rng, R, trials, p_cls=(0.15, 0.6, 0.25)):
+    """Q = A(c, c) + A(c, u) E of a robot standing on one or two flat feet (6-DOF bodies, inertias spread over 1e2), some friction rows on
+    their bound folded into their normal's column: non-symmetric, R x R with the rows / columns outside the clamping set zero.  p_cls: the
+    shares of not clamping / clamping / upper-bound rows.  Yields (trial, Q, rows in the clamping set, rank, cond) for the matrices
+    with cond <= 1e8 (beyond it there is no clear gap between the singular values that count and round-off)."""
+    NC = R // 3
+    for trial in range(trials):
+        nb = int(rng.integers(1, 3))                                   # one or two 6-DOF bodies
+        J = np.zeros((R, 6 * nb))
+        for cidx in range(NC):                                          # contact -> body, point on its sole
+            bdy = int(rng.integers(0, nb)); pt = np.array([rng.uniform(-0.1, 0.1), 0.0, rng.uniform(-0.05, 0.05)])
+            for ax in range(3):
+                d = np.eye(3)[[1, 0, 2][ax]]
+                J[3 * cidx + ax, 6 * bdy:6 * bdy + 3] = np.cross(pt, d); J[3 * cidx + ax, 6 * bdy + 3:6 * bdy + 6] = d
+        Lam = np.zeros((6 * nb, 6 * nb))
+        for bdy in range(nb):
+            M = rng.normal(0, 1, (6, 6)); Lam[6 * bdy:6 * bdy + 6, 6 * bdy:6 * bdy + 6] = M @ np.diag(10 ** rng.uniform(-1, 1, 6)) @ M.T
+        A = J @ Lam @ J.T
+        cls = rng.choice([0, 1, 2], size=R, p=list(p_cls))             # not clamping / clamping / upper bound (friction rows only)
+        cls[0::3] = np.where(cls[0::3] == 2, 1, cls[0::3])
+        Q = np.zeros((R, R))
+        cl = np.where(cls == 1)[0]
+        if len(cl) == 0:
+            continue
+        Q[np.ix_(cl, cl)] = A[np.ix_(cl, cl)]
+        for u in np.where(cls == 2)[0]:
+            nrm = u - u % 3
+            if cls[nrm] == 1:
+                Q[cl, nrm] += rng.choice([-1.0, 1.0]) * rng.uniform(0.3, 1.0) * A[cl, u]
+        sub = Q[np.ix_(cl, cl)]
+        sv = np.linalg.svd(sub, compute_uv=False)
+        k = int((sv > 1e-12 * sv[0]).sum())
+        cond = sv[0] / sv[k - 1]
+        if cond > 1e8:
+            continue
+        yield trial, Q, len(cl), k, cond
+
+
+# ---- the saved record of a step (SavedLayout, csrc/model_dev.hpp / nimble_amd.hip) ----
+def record_rows(world, saved, B, max_contacts=8, cr_size=22):
+    """x, b, cls, cfm, pflag rows, the Delassus matrix A and the pinv block of the saved record of the 24- / 48-row builds, on the device."""
+    import torch
+    n = world.n
+    max_rows = 3 * max_contacts
+    rec = saved.view(torch.float64)
+    x0 = 5 * n + 1 + max_contacts * cr_size
+    b0, cls0, cfm0 = x0 + max_rows, x0 + 2 * max_rows, x0 + 3 * max_rows
+    pflag0 = x0 + 4 * max_rows
+    total = pflag0 + 1 + max_contacts
+    pinv_off = max_rows * max_rows + 2 * n * max_rows
+    dense = pinv_off + max_rows * max_rows
+    rows = rec[: total * B].view(total, B)
+    blocks = rec[total * B: total * B + B * dense].view(B, dense)
+    pflag = rows[pflag0]
+    pinv = torch.where((pflag != 0)[:, None], blocks[:, pinv_off:pinv_off + max_rows * max_rows], torch.zeros((), dtype=torch.float64, device=rec.device))
+    return {"nc": rows[5 * n], "x": rows[x0:x0 + max_rows].t(), "b": rows[b0:b0 + max_rows].t(), "cls": rows[cls0:cls0 + max_rows].t(),
+            "cfm": rows[cfm0:cfm0 + max_rows].t(), "contacts": rows[5 * n + 1:x0].t(), "A": blocks[:, :max_rows * max_rows],
+            "pflag": pflag, "pinv": pinv}       # (pinv of a world without the flag is whatever the buffer held: zeroed)
