@@ -240,7 +240,9 @@ const char* nbl_last_error(void);
  *            entries above - neither the model description nor any existing call changed; a caller that needs them looks the symbols up).
  *            + nbl_body_set_create, nbl_body_set_destroy, nbl_body_set_mass, nbl_body_set_origin_moments, nbl_centroidal_workspace_bytes,
  *            nbl_centroidal_forward, nbl_centroidal_backward and the NBL_CEN_* flags (centre of mass, momentum and energy of a body set,
- *            below: appended without a new minor number, like the entries above). */
+ *            below: appended without a new minor number, like the entries above).
+ *            + nbl_sensors_workspace_bytes, nbl_sensors_forward, nbl_sensors_backward (gyroscope, accelerometer and magnetometer readings
+ *            of a sensor set, below: appended without a new minor number, like the entries above). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -770,6 +772,32 @@ int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* s, int64_t B, 
                                 const double* g_com, const double* g_com_vel, const double* g_com_acc, const double* g_momentum,
                                 const double* g_ke, const double* g_pe, double* grad_state, double* grad_accel, int32_t accumulate,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- gyroscope, accelerometer and magnetometer readings (csrc/sensors.hip) -----------------------------------------------------------------------
+ * Skeleton::getGyroReadings / getAccelerometerReadings / getMagnetometerReadings (dart/dynamics/Skeleton.cpp:8082-8460) for B worlds, and
+ * their exact vector-Jacobian product.
+ *
+ * A SENSOR SET is an nbl_kin_map whose entries are all NBL_KIN_SPATIAL (any other kind: NBL_E_BADARG), like a wrench set: entry e names
+ * the sensor frame T_bs = (R_bs, p_bs) = T_offset[e] fixed in body[e] (at most 64 entries; body -1: a sensor fixed in the world).  With the
+ * body's spatial velocity [w; v] and spatial acceleration [al; a] in body coordinates (no gravity in it), its world rotation R, the
+ * model's gravity g and a world-frame magnetic field m, rows 3 e .. 3 e + 2 of the outputs are
+ *   gyro = R_bs^T w          acc = R_bs^T (a + al x p_bs + w x (v + w x p_bs) - R^T g)          mag = R_bs^T R^T m
+ * (a sensor in the world: gyro 0, acc -R_bs^T g, mag R_bs^T m).  Body scales do not exist here: they are 1.
+ *
+ * nbl_sensors_forward writes every output that is not NULL (device pointers, SoA: state [2n][B] = [q; v], accel [n][B], field [3][B],
+ * gyro / acc / mag [3 count][B]).  acc without accel and mag without field: NBL_E_BADARG.
+ * nbl_sensors_backward: grad_state [2n][B], grad_accel [n][B] and grad_field [3][B] (any may be NULL) = (accumulate: +=) the cotangents
+ * g_gyro, g_acc, g_mag [3 count][B] (any may be NULL: zero) pulled back through the forward function, exactly, in the library's own
+ * coordinates: the dependence of the velocity products on q and v and of R^T g on q is included; ball and free coordinates go through
+ * expMapJac.  g_acc needs accel, g_mag needs field.
+ * workspace: nbl_sensors_workspace_bytes(m, B) bytes of device scratch (54 doubles per body and world; one size serves both calls).
+ * Stream-ordered, no device synchronisation, no use of the handle's slices; B may be (T + 1) x worlds. */
+size_t nbl_sensors_workspace_bytes(const nbl_model* m, int64_t B);
+int32_t nbl_sensors_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
+                            double* gyro, double* acc, double* mag, void* workspace, size_t workspace_bytes, void* stream);
+int32_t nbl_sensors_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
+                             const double* g_gyro, const double* g_acc, const double* g_mag, double* grad_state, double* grad_accel,
+                             double* grad_field, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* enabled = 0: off (and reset); 1: HIP events around every kernel launch; N > 1: around the launches of every N-th forward /
  * backward call only (sampling keeps the perturbation of a timed region below 1 %). */

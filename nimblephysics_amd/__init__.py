@@ -13,7 +13,8 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "IKConfig", "contact_inverse_dynamics",
            "inverse_dynamics_from_predictions", "read_contacts", "body_contact_wrenches", "rollout_contacts",
            "rollout_body_contact_wrenches", "ContactReadout", "center_of_mass", "com_velocity", "com_acceleration", "centroidal_momentum",
-           "kinetic_energy", "potential_energy", "com_jacobian", "centroidal", "Centroidal"]
+           "kinetic_energy", "potential_energy", "com_jacobian", "centroidal", "Centroidal", "gyro_readings", "accelerometer_readings",
+           "magnetometer_readings", "imu_readings", "IMUReadings", "gyro_jacobian", "accelerometer_jacobian", "magnetometer_jacobian"]
 
 
 def __getattr__(name):
@@ -55,6 +56,10 @@ def __getattr__(name):
         import importlib                                    # (not `from . import`: "centroidal" is also the name asked for here)
         _cen = importlib.import_module(".centroidal", __name__)
         return _cen if name == "centroidal" else getattr(_cen, name)       # the module answers a call like its function centroidal()
+    if name in ("gyro_readings", "accelerometer_readings", "magnetometer_readings", "imu_readings", "IMUReadings", "gyro_jacobian",
+                "accelerometer_jacobian", "magnetometer_jacobian"):
+        from . import sensors as _s
+        return getattr(_s, name)
     if name in ("timestep", "TimestepLayer", "rollout", "RolloutLayer"):
         from . import timestep as _t
         return getattr(_t, name)

@@ -178,6 +178,12 @@ def lib():
     L.nbl_centroidal_forward.restype = C.c_int32
     L.nbl_centroidal_backward.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
     L.nbl_centroidal_backward.restype = C.c_int32
+    L.nbl_sensors_workspace_bytes.argtypes = [vp, C.c_int64]
+    L.nbl_sensors_workspace_bytes.restype = C.c_size_t
+    L.nbl_sensors_forward.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nbl_sensors_forward.restype = C.c_int32
+    L.nbl_sensors_backward.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_sensors_backward.restype = C.c_int32
     _lib = L
     return L
 
@@ -198,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "nbl_forward_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_backward", "nbl_contact_inverse_dynamics",
     "nbl_contact_readout", "nbl_contact_readout_rows", "nbl_contact_body_wrenches",
     "nbl_body_set_create", "nbl_body_set_destroy", "nbl_body_set_mass", "nbl_body_set_origin_moments", "nbl_centroidal_workspace_bytes", "nbl_centroidal_forward", "nbl_centroidal_backward",
+    "nbl_sensors_workspace_bytes", "nbl_sensors_forward", "nbl_sensors_backward",
 ]
 
 

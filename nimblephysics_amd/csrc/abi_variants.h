@@ -105,6 +105,9 @@
 #define nbl_centroidal_workspace_bytes NBL_V(nbl_centroidal_workspace_bytes)
 #define nbl_centroidal_forward NBL_V(nbl_centroidal_forward)
 #define nbl_centroidal_backward NBL_V(nbl_centroidal_backward)
+#define nbl_sensors_workspace_bytes NBL_V(nbl_sensors_workspace_bytes)
+#define nbl_sensors_forward NBL_V(nbl_sensors_forward)
+#define nbl_sensors_backward NBL_V(nbl_sensors_backward)
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

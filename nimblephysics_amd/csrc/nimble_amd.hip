@@ -28,6 +28,7 @@
 #include "kinematics.hip"
 #include "dynamics.hip"
 #include "centroidal.hip"
+#include "sensors.hip"
 #include "ik.hip"
 #include "contact_readout.hip"
 
@@ -2329,6 +2330,60 @@ int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* set, int64_t B
                                              g_com, g_com_vel, g_com_acc, g_momentum, g_ke, g_pe, grad_state, grad_accel, accumulate ? 1 : 0,
                                              (double*)workspace));
   m->timingNow = false;
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// ---- gyroscope, accelerometer and magnetometer readings of a sensor set (csrc/sensors.hip) ---------------------------------------------------
+size_t nbl_sensors_workspace_bytes(const nbl_model* m, int64_t B) { return nbl_centroidal_workspace_bytes(m, B); }
+
+// the checks the two sensor calls share; a sensor set is a kinematics map of NBL_KIN_SPATIAL entries, like a wrench set
+static int32_t sensCheck(const nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const void* workspace, size_t workspace_bytes) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (!k) return fail(NBL_E_BADARG, "null sensor set");
+  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  for (int e = 0; e < k->count; e++)
+    if (k->hEntries[e].kind != KIN_SPATIAL)
+      return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the sensor set is not NBL_KIN_SPATIAL: a sensor needs a whole frame");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (B == 0) return NBL_OK;
+  if (!state) return fail(NBL_E_BADARG, "null argument");
+  if ((B + SENS_BLOCK - 1) / SENS_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  const size_t need = nbl_sensors_workspace_bytes(m, B);
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "sensor workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_sensors_workspace_bytes() = " + std::to_string(need));
+  return NBL_OK;
+}
+
+int32_t nbl_sensors_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
+                            double* gyro, double* acc, double* mag, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = sensCheck(m, k, B, state, workspace, workspace_bytes);
+  if (rc != NBL_OK) return rc;
+  if (acc && !accel) return fail(NBL_E_BADARG, "acc needs the accelerations (accel is null)");
+  if (mag && !field) return fail(NBL_E_BADARG, "mag needs the magnetic field (field is null)");
+  if (B == 0 || !(gyro || acc || mag)) return NBL_OK;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_sensors, dim3((unsigned)((B + SENS_BLOCK - 1) / SENS_BLOCK)), dim3(SENS_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, B, state, accel, field,
+                     gyro, acc, mag, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t nbl_sensors_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
+                             const double* g_gyro, const double* g_acc, const double* g_mag, double* grad_state, double* grad_accel,
+                             double* grad_field, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = sensCheck(m, k, B, state, workspace, workspace_bytes);
+  if (rc != NBL_OK) return rc;
+  if (g_acc && !accel) return fail(NBL_E_BADARG, "g_acc needs the accelerations (accel is null)");
+  if (g_mag && !field) return fail(NBL_E_BADARG, "g_mag needs the magnetic field (field is null)");
+  if (B == 0 || (!grad_state && !grad_accel && !grad_field)) return NBL_OK;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_sensors_vjp, dim3((unsigned)((B + SENS_BLOCK - 1) / SENS_BLOCK)), dim3(SENS_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, B, state, accel, field,
+                     g_gyro, g_acc, g_mag, grad_state, grad_accel, grad_field, accumulate ? 1 : 0, (double*)workspace);
   HIP_TRY(hipGetLastError());
   return NBL_OK;
 }

@@ -110,7 +110,12 @@
                                     double*, double*, double*, void*, size_t, void*);                                                      \
   int32_t nbl_centroidal_backward##S(void*, const void*, int64_t, const double*, const double*, int32_t, const double*, const double*,     \
                                      const double*, const double*, const double*, const double*, double*, double*, int32_t, void*, size_t, \
-                                     void*);
+                                     void*);                                                                                               \
+  size_t nbl_sensors_workspace_bytes##S(const void*, int64_t);                                                                             \
+  int32_t nbl_sensors_forward##S(void*, const void*, int64_t, const double*, const double*, const double*, double*, double*, double*,      \
+                                 void*, size_t, void*);                                                                                    \
+  int32_t nbl_sensors_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, const double*, const double*,  \
+                                  const double*, double*, double*, double*, int32_t, void*, size_t, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -193,6 +198,9 @@ struct Variant {
   size_t (*centroidal_workspace_bytes)(const void*, int64_t);
   int32_t (*centroidal_forward)(void*, const void*, int64_t, const double*, const double*, int32_t, double*, double*, double*, double*, double*, double*, double*, void*, size_t, void*);
   int32_t (*centroidal_backward)(void*, const void*, int64_t, const double*, const double*, int32_t, const double*, const double*, const double*, const double*, const double*, const double*, double*, double*, int32_t, void*, size_t, void*);
+  size_t (*sensors_workspace_bytes)(const void*, int64_t);
+  int32_t (*sensors_forward)(void*, const void*, int64_t, const double*, const double*, const double*, double*, double*, double*, void*, size_t, void*);
+  int32_t (*sensors_backward)(void*, const void*, int64_t, const double*, const double*, const double*, const double*, const double*, const double*, double*, double*, double*, int32_t, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -210,7 +218,8 @@ struct Variant {
    nbl_inverse_dynamics_wrench_backward##S, nbl_forward_dynamics_wrench_forward##S, nbl_forward_dynamics_wrench_backward##S,                \
    nbl_contact_inverse_dynamics##S, nbl_contact_readout##S, nbl_contact_readout_rows##S, nbl_contact_body_wrenches##S,       \
    nbl_body_set_create##S, nbl_body_set_destroy##S, nbl_body_set_mass##S, nbl_body_set_origin_moments##S,         \
-   nbl_centroidal_workspace_bytes##S, nbl_centroidal_forward##S, nbl_centroidal_backward##S}
+   nbl_centroidal_workspace_bytes##S, nbl_centroidal_forward##S, nbl_centroidal_backward##S,                         \
+   nbl_sensors_workspace_bytes##S, nbl_sensors_forward##S, nbl_sensors_backward##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -566,6 +575,22 @@ int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* s, int64_t B, 
   if (m && s->v != m->v) return ownError(NBL_E_BADARG, "the body set was made for another model");
   return NBL_FWD(m, centroidal_backward, s->impl, B, state, accel, flags, g_com, g_com_vel, g_com_acc, g_momentum, g_ke, g_pe, grad_state,
                  grad_accel, accumulate, workspace, workspace_bytes, stream);
+}
+
+size_t nbl_sensors_workspace_bytes(const nbl_model* m, int64_t B) { return m ? m->v->sensors_workspace_bytes(m->impl, B) : 0; }
+int32_t nbl_sensors_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
+                            double* gyro, double* acc, double* mag, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!k) return ownError(NBL_E_BADARG, "null sensor set");
+  if (m && k->v != m->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model");
+  return NBL_FWD(m, sensors_forward, k->impl, B, state, accel, field, gyro, acc, mag, workspace, workspace_bytes, stream);
+}
+int32_t nbl_sensors_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
+                             const double* g_gyro, const double* g_acc, const double* g_mag, double* grad_state, double* grad_accel,
+                             double* grad_field, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!k) return ownError(NBL_E_BADARG, "null sensor set");
+  if (m && k->v != m->v) return ownError(NBL_E_BADARG, "the kinematics map was made for another model");
+  return NBL_FWD(m, sensors_backward, k->impl, B, state, accel, field, g_gyro, g_acc, g_mag, grad_state, grad_accel, grad_field, accumulate,
+                 workspace, workspace_bytes, stream);
 }
 
 void nbl_ik_default_config(nbl_ik_config* c) { nbl_ik_default_config_c8(c); }   // (the same in every instantiation)

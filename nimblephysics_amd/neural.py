@@ -14,6 +14,7 @@ import torch
 from ._lib import NimbleAmdError
 from .world import World
 from .mapping import IKMapping  # noqa: F401  (nimble.neural.IKMapping)
+from .sensors import WRT_ACCELERATION, WRT_POSITION, WRT_VELOCITY  # noqa: F401  (nimble.neural.WRT_*: the `wrt` of the sensor Jacobians)
 
 
 class LossGradient:

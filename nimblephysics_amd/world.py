@@ -437,6 +437,42 @@ class World:
         from .centroidal import CEN_PE_BODY_ORIGIN, world_centroidal
         return world_centroidal(self, 5, skeleton, flags=CEN_PE_BODY_ORIGIN)
 
+    # ---- inertial sensors on the current state (sensors.py; Skeleton.cpp:8082-8460).  sensors: [(body name or index, 4 x 4 or None)] ----
+    def getGyroReadings(self, sensors) -> torch.Tensor:
+        """Skeleton::getGyroReadings: [B, 3 S]."""
+        from .sensors import world_readings
+        return world_readings(self, 0, sensors)
+
+    def getAccelerometerReadings(self, sensors, accelerations) -> torch.Tensor:
+        """Skeleton::getAccelerometerReadings at the joint accelerations [B, n] ([n]): [B, 3 S]; a body at rest reads -g in its frame."""
+        from .sensors import world_readings
+        return world_readings(self, 1, sensors, accelerations=accelerations)
+
+    def getMagnetometerReadings(self, sensors, field) -> torch.Tensor:
+        """Skeleton::getMagnetometerReadings of the world-frame field [3] ([B, 3]): [B, 3 S]."""
+        from .sensors import world_readings
+        return world_readings(self, 2, sensors, field=field)
+
+    def getGyroReadingsJacobianWrt(self, sensors, wrt) -> torch.Tensor:
+        """Skeleton::getGyroReadingsJacobianWrt, wrt = neural.WRT_POSITION / WRT_VELOCITY / WRT_ACCELERATION: [B, 3 S, n]."""
+        from .sensors import world_jacobian
+        return world_jacobian(self, 0, sensors, wrt)
+
+    def getAccelerometerReadingsJacobianWrt(self, sensors, accelerations, wrt) -> torch.Tensor:
+        """Skeleton::getAccelerometerReadingsJacobianWrt at the joint accelerations [B, n]: [B, 3 S, n]."""
+        from .sensors import world_jacobian
+        return world_jacobian(self, 1, sensors, wrt, accelerations=accelerations)
+
+    def getMagnetometerReadingsJacobianWrt(self, sensors, field, wrt) -> torch.Tensor:
+        """Skeleton::getMagnetometerReadingsJacobianWrt: [B, 3 S, n]."""
+        from .sensors import world_jacobian
+        return world_jacobian(self, 2, sensors, wrt, field=field)
+
+    def getMagnetometerReadingsJacobianWrtMagneticField(self, sensors, field) -> torch.Tensor:
+        """Skeleton::getMagnetometerReadingsJacobianWrtMagneticField: [B, 3 S, 3]."""
+        from .sensors import WRT_FIELD, world_jacobian
+        return world_jacobian(self, 2, sensors, WRT_FIELD, field=field)
+
     def reset_lcp_cache(self):
         self.lcp_cache = None
 
