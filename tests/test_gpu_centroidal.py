@@ -31,7 +31,9 @@ def _rel(a, b):
 def _model(name):
     import nimblephysics_amd as na
     from test_ball_joint import ball_model
-    return {"cartpole": na.cartpole, "ball_arm": lambda: ball_model(2, True), "atlas20_ground": lambda: na.atlas("atlas20", ground=True),
+    from test_screw_joint import screw_arm
+    return {"screw_arm": lambda: screw_arm(2, True), "screw_root": lambda: screw_arm(2, False),
+            "cartpole": na.cartpole, "ball_arm": lambda: ball_model(2, True), "atlas20_ground": lambda: na.atlas("atlas20", ground=True),
             "atlas33": lambda: na.atlas("atlas33"), "atlas20": lambda: na.atlas("atlas20"), "pendulum": na.single_pendulum}[name]()
 
 
@@ -59,7 +61,7 @@ def _reference(name, md, S, A, cots, fd_worlds):
 
 
 @pytest.mark.parametrize("B", [1, 63, 65, 130])
-@pytest.mark.parametrize("name", ["cartpole", "ball_arm", "atlas20_ground", "atlas33"])
+@pytest.mark.parametrize("name", ["cartpole", "ball_arm", "atlas20_ground", "atlas33", "screw_arm", "screw_root"])
 def test_device_equals_cen_numpy_and_the_host_build(name, B):
     """Every world is checked.  The states of the smaller batches are the first worlds of the largest one, so the reference is computed once
     per model.  Forward outputs, closed-form gradients and the comparison with the host build cover EVERY world; the finite-difference

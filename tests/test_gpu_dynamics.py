@@ -95,14 +95,16 @@ def test_gradcheck(which):
     assert torch.autograd.gradcheck(lambda s: na.mass_matrix(w, s), (st,), **kw)
 
 
-@pytest.mark.parametrize("name", ["atlas20", "ball_arm", "free_below_root"])
+@pytest.mark.parametrize("name", ["atlas20", "ball_arm", "free_below_root", "screw_arm", "screw_root"])
 def test_the_device_kernels_equal_the_host_build_to_1e_13(name):
     """See the head of this file: 1e-13 relative (fused multiply-adds and sincos differ from the host build), not bit for bit."""
     import nimblephysics_amd as na
     from test_ball_joint import ball_model
     from test_dynamics_host import ShimDynamics, free_below_root, load_shim
+    from test_screw_joint import screw_arm
     from nimblephysics_amd.dynamics import ID_JOINT_FORCES, inverse_dynamics_soa, inverse_dynamics_vjp_soa, mass_matrix_soa
-    md = {"atlas20": lambda: na.atlas("atlas20"), "ball_arm": lambda: ball_model(2, True), "free_below_root": free_below_root}[name]()
+    md = {"atlas20": lambda: na.atlas("atlas20"), "ball_arm": lambda: ball_model(2, True), "free_below_root": free_below_root,
+          "screw_arm": lambda: screw_arm(2, True), "screw_root": lambda: screw_arm(2, False)}[name]()
     host = ShimDynamics(load_shim(), md)
     w = na.World(md, device=DEV)
     S, A, g = _states(md, 128, 6)

@@ -30,15 +30,16 @@ TOL = 1e-10                       # measured oracle disagreement <= 1.2e-13: see
 ORACLE_ROUTES_MAX = 1e-11
 BLOCK = 64                        # DYN_BLOCK of csrc/dynamics.hip
 B_PARITY = 2 * BLOCK + 3          # two full workgroups and a partial one
-PARITY_MODELS = ["atlas20", "ball_arm", "free_below_root", "cartpole"]
+PARITY_MODELS = ["atlas20", "ball_arm", "free_below_root", "cartpole", "screw_arm", "screw_root"]
 
 
 def _model(name):
     import nimblephysics_amd as na
     from test_ball_joint import ball_model
     from test_dynamics_host import free_below_root
+    from test_screw_joint import screw_arm
     return {"atlas20": lambda: na.atlas("atlas20"), "ball_arm": lambda: ball_model(2, True), "free_below_root": free_below_root,
-            "cartpole": na.cartpole}[name]()
+            "cartpole": na.cartpole, "screw_arm": lambda: screw_arm(2, True), "screw_root": lambda: screw_arm(2, False)}[name]()
 
 
 def _joint_forces(md, q, v):
@@ -150,7 +151,7 @@ def test_gradcheck(name):
 
 
 @gpu
-@pytest.mark.parametrize("name", ["atlas20", "ball_arm", "free_below_root"])
+@pytest.mark.parametrize("name", ["atlas20", "ball_arm", "free_below_root", "screw_arm", "screw_root"])
 def test_the_device_kernels_equal_the_host_build_to_1e_13(name):
     """See the head of this file: 1e-13 relative, not bit for bit."""
     import nimblephysics_amd as na

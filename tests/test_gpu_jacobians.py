@@ -50,7 +50,7 @@ def test_state_and_action_jacobians_vs_finite_differences(contact):
         assert np.abs(fd - JA[:, :, j]).max() <= 2e-5 * scale
 
 
-@pytest.mark.parametrize("case", ["cartpole", "atlas20_freefall", "atlas20_contact", "atlas20_contact_noisy", "box_stack", "partial_action_space"])
+@pytest.mark.parametrize("case", ["cartpole", "atlas20_freefall", "atlas20_contact", "atlas20_contact_noisy", "box_stack", "partial_action_space", "screw_walker"])
 def test_state_and_action_jacobians_equal_the_oracles_dense_jacobians(case):
     """The parity test proper (the reference's World::getStateJacobian / getActionJacobian, World.cpp:2210-2243, restated by
     the oracle from its five dense blocks posPos / velPos / posVel / velVel / forceVel exactly like BackpropSnapshot forms them):
@@ -71,6 +71,10 @@ def test_state_and_action_jacobians_equal_the_oracles_dense_jacobians(case):
         md, s, a = contact_inputs("atlas20", B, 64, joint_noise=0.02, vel_noise=0.01, action_noise=0.0)
     elif case == "box_stack":
         md, s, a = box_stack_inputs(B, 65)
+    elif case == "screw_walker":                # contacts on screw-jointed limbs, a free screw-jointed tail (tests/test_screw_joint.py)
+        from test_screw_joint import contact_scene
+        md, s, a = contact_scene("screw_walker", 8)
+        s, a = s[:B], a[:B]
     else:
         md, s, a = cfg_inputs("atlas20", B, 66)
         md.set_action_space([6, 9, 12, 19])
@@ -93,6 +97,7 @@ def test_state_and_action_jacobians_equal_the_oracles_dense_jacobians(case):
     # free-joint position blocks: the oracle restates the reference's central differences (FreeJoint.cpp:950-1007), the
     # device uses the exact expression; they agree to ~1e-9, everything else to round-off
     tol = 1e-7 if case != "box_stack" else 1e-5      # cubes with yaw ~ U(-pi, pi): d logMap near |yaw| = pi amplifies the FD error
+    print(f"[{case}] dense Jacobians against the oracle's: state {worst_s:.2e}, action {worst_a:.2e}")
     assert worst_s < tol and worst_a < tol, (case, worst_s, worst_a)
 
 

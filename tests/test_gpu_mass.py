@@ -64,6 +64,7 @@ def _check(md, entries, s, a, seed, tol=2e-6, second_eps=None, max_outliers=0.0,
     # max_outliers: share of (world, parameter) entries allowed to miss: a finite difference of the ORACLE across an LCP kink
     # (the perturbed step resolves on another branch at both step sizes) is not a derivative
     bad = err >= tol
+    print(f"[mass gradient, {md.name}, {[(b, int(t)) for b, t in entries]}] worst error over scale {err.max():.2e} (tol {tol:g}), share above it {bad.mean():.4f}")
     assert bad.mean() <= max_outliers, (float(bad.mean()), err.max(), np.unravel_index(err.argmax(), err.shape), dev[0], ref[0])
 
 
