@@ -242,7 +242,9 @@ const char* nbl_last_error(void);
  *            nbl_centroidal_forward, nbl_centroidal_backward and the NBL_CEN_* flags (centre of mass, momentum and energy of a body set,
  *            below: appended without a new minor number, like the entries above).
  *            + nbl_sensors_workspace_bytes, nbl_sensors_forward, nbl_sensors_backward (gyroscope, accelerometer and magnetometer readings
- *            of a sensor set, below: appended without a new minor number, like the entries above). */
+ *            of a sensor set, below: appended without a new minor number, like the entries above).
+ *            + nbl_inverse_dynamics_backward_inertia, nbl_forward_dynamics_backward_inertia (gradients of the dynamics calls to the
+ *            registered inertia parameters, below: appended without a new minor number, like the entries above). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -596,6 +598,33 @@ int32_t nbl_forward_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, 
 int32_t nbl_forward_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
                                              const double* wrench, int32_t flags, const double* grad_accel, double* grad_state, double* grad_tau,
                                              double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- gradients of the dynamics calls to the registered inertia parameters (csrc/dynamics.hip) -------------------------------------------
+ * Skeleton::getJacobianOfID / getJacobianOfC / getJacobianOfM / getJacobianOfMinv / getJacobianOfFD with a WithRespectTo that is the mass
+ * vector (dart/dynamics/Skeleton.hpp:650-718; the reference finite-differences them), as vector-Jacobian products for B worlds.  The
+ * parameters are the table of nbl_set_inertia_params[_on] (count = nbl_num_inertia_params(m)); inverse dynamics is linear in every body's
+ * spatial inertia G_i, so with V_i, A_i the body's twist and acceleration (gravity carried as the base acceleration -g) and Fb_i the
+ * twist field the cotangent generates,
+ *   d(grad_tau^T tau) / d theta_p = Fb_i . (dG_p A_i) - ad(V_i, Fb_i) . (dG_p V_i),   i = the body of parameter p:
+ * one root -> leaf sweep and one contraction per parameter, one world per lane, in closed form.
+ *   nbl_inverse_dynamics_backward_inertia: grad_params [count][B] = (accumulate: +=) (d tau / d theta)^T grad_tau of
+ *     nbl_inverse_dynamics_forward under the same state, accel (NULL: a = 0) and flags.  The NBL_ID_JOINT_FORCES terms and wrenches on
+ *     bodies do not depend on the inertias: the call serves nbl_inverse_dynamics_wrench_forward unchanged.
+ *     workspace: nbl_dynamics_workspace_bytes(m, B).
+ *   nbl_forward_dynamics_backward_inertia: grad_params = (+=) (d a / d theta)^T grad_accel = -(d ID / d theta)^T lambda at (q, v, a),
+ *     lambda = M^-1 grad_accel, of nbl_forward_dynamics_forward (k NULL: wrench is not read) or nbl_forward_dynamics_wrench_forward
+ *     (k, wrench as there; NBL_WRENCH_WORLD accepted): two launches, a and lambda by the articulated-body recursion, then the contraction.
+ *     workspace: nbl_forward_dynamics_workspace_bytes(m, B), or nbl_wrench_workspace_bytes(m, k, B) when k is given.
+ * Both are self-contained (no preceding backward call, unlike nbl_backward_inertia), read the handle's CURRENT inertias, are stream-ordered
+ * on `stream` without synchronisation, do not use the handle's slices, use no atomics and are bit-reproducible and independent of B and
+ * of a world's place in the batch; B may be (T + 1) x worlds.  Per-world results: the caller sums over b for a loss over the batch.
+ * No parameter registered, or B = 0: a no-op that returns NBL_OK.  Errors as for the calls they differentiate (NBL_E_BADARG, also for a
+ * NULL grad_params when count > 0; NBL_E_WORKSPACE): nothing is launched then. */
+int32_t nbl_inverse_dynamics_backward_inertia(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
+                                              const double* grad_tau, double* grad_params, int32_t accumulate, void* workspace,
+                                              size_t workspace_bytes, void* stream);
+int32_t nbl_forward_dynamics_backward_inertia(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                              const double* wrench, int32_t flags, const double* grad_accel, double* grad_params,
+                                              int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 /* Contact inverse dynamics (Skeleton::getContactInverseDynamics, getMultipleContactInverseDynamics; Skeleton.cpp:9705-9949): the wrenches
  * wrench_out [6 E][B] on the entries' frames (local coordinates) under which the accelerations accel [n][B] need NO torque on the six
  * coordinates of the free root joint above them, and the joint torques tau [n][B] = M a + C - J^T W that go with them (the root's six rows

@@ -14,7 +14,8 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "inverse_dynamics_from_predictions", "read_contacts", "body_contact_wrenches", "rollout_contacts",
            "rollout_body_contact_wrenches", "ContactReadout", "center_of_mass", "com_velocity", "com_acceleration", "centroidal_momentum",
            "kinetic_energy", "potential_energy", "com_jacobian", "centroidal", "Centroidal", "gyro_readings", "accelerometer_readings",
-           "magnetometer_readings", "imu_readings", "IMUReadings", "gyro_jacobian", "accelerometer_jacobian", "magnetometer_jacobian"]
+           "magnetometer_readings", "imu_readings", "IMUReadings", "gyro_jacobian", "accelerometer_jacobian", "magnetometer_jacobian",
+           "inverse_dynamics_mass_gradient", "forward_dynamics_mass_gradient", "inverse_dynamics_mass_jacobian", "forward_dynamics_mass_jacobian"]
 
 
 def __getattr__(name):
@@ -45,7 +46,8 @@ def __getattr__(name):
         from . import mapping as _m
         return getattr(_m, name)
     if name in ("inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics", "multiply_by_inv_mass_matrix", "inv_mass_matrix",
-                "contact_inverse_dynamics", "inverse_dynamics_from_predictions"):
+                "contact_inverse_dynamics", "inverse_dynamics_from_predictions", "inverse_dynamics_mass_gradient", "forward_dynamics_mass_gradient",
+                "inverse_dynamics_mass_jacobian", "forward_dynamics_mass_jacobian"):
         from . import dynamics as _d
         return getattr(_d, name)
     if name in ("read_contacts", "body_contact_wrenches", "rollout_contacts", "rollout_body_contact_wrenches", "ContactReadout"):

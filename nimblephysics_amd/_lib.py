@@ -184,6 +184,10 @@ def lib():
     L.nbl_sensors_forward.restype = C.c_int32
     L.nbl_sensors_backward.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
     L.nbl_sensors_backward.restype = C.c_int32
+    L.nbl_inverse_dynamics_backward_inertia.argtypes = [vp, C.c_int64, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_inverse_dynamics_backward_inertia.restype = C.c_int32
+    L.nbl_forward_dynamics_backward_inertia.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_forward_dynamics_backward_inertia.restype = C.c_int32
     _lib = L
     return L
 
@@ -205,6 +209,7 @@ EXPORTED_SYMBOLS = [
     "nbl_contact_readout", "nbl_contact_readout_rows", "nbl_contact_body_wrenches",
     "nbl_body_set_create", "nbl_body_set_destroy", "nbl_body_set_mass", "nbl_body_set_origin_moments", "nbl_centroidal_workspace_bytes", "nbl_centroidal_forward", "nbl_centroidal_backward",
     "nbl_sensors_workspace_bytes", "nbl_sensors_forward", "nbl_sensors_backward",
+    "nbl_inverse_dynamics_backward_inertia", "nbl_forward_dynamics_backward_inertia",
 ]
 
 

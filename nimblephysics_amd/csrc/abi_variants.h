@@ -94,6 +94,8 @@
 #define nbl_forward_dynamics_wrench_forward NBL_V(nbl_forward_dynamics_wrench_forward)
 #define nbl_forward_dynamics_wrench_backward NBL_V(nbl_forward_dynamics_wrench_backward)
 #define nbl_contact_inverse_dynamics NBL_V(nbl_contact_inverse_dynamics)
+#define nbl_inverse_dynamics_backward_inertia NBL_V(nbl_inverse_dynamics_backward_inertia)
+#define nbl_forward_dynamics_backward_inertia NBL_V(nbl_forward_dynamics_backward_inertia)
 #define nbl_contact_readout NBL_V(nbl_contact_readout)
 #define nbl_contact_readout_rows NBL_V(nbl_contact_readout_rows)
 #define nbl_contact_body_wrenches NBL_V(nbl_contact_body_wrenches)

@@ -35,6 +35,19 @@ __global__ __launch_bounds__(DYN_BLOCK) void k_inverse_dynamics_vjp(const DevBod
   idVjpWorld(bodies, dofs, mdl.nb, mdl.n, mdl.gravity, mdl.dt, flags, B, b, state, accel, gtau, gstate, gaccel, accumulate, ws);
 }
 
+// grad_params [count][B] (= or +=) (d tau / d theta)^T grad_tau for the registered inertia parameters: sweep 1 of the kernel above, then
+// one contraction per parameter.  The table is wave-uniform (scalar loads), V / A / Fb of the parameter's body come back as [slot][B]
+// lines, and so does the output.
+__global__ __launch_bounds__(DYN_BLOCK) void k_inverse_dynamics_inertia_vjp(const DevBody* __restrict__ bodies, DevModel mdl, int flags, int64_t B,
+                                                                            const double* __restrict__ state, const double* __restrict__ accel,
+                                                                            const double* __restrict__ gtau,
+                                                                            const DevInertiaParam* __restrict__ params, int count,
+                                                                            double* __restrict__ gparams, int accumulate, double* __restrict__ ws) {
+  const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;
+  if (b >= B) return;
+  idInertiaVjpWorld(bodies, mdl.nb, mdl.n, mdl.gravity, flags, B, b, state, accel, gtau, params, count, gparams, accumulate, ws);
+}
+
 __global__ __launch_bounds__(DYN_BLOCK) void k_mass_matrix(const DevBody* __restrict__ bodies, DevModel mdl, int64_t B,
                                                            const double* __restrict__ state, double* __restrict__ M, double* __restrict__ ws) {
   const int64_t b = (int64_t)blockIdx.x * DYN_BLOCK + threadIdx.x;

@@ -86,6 +86,13 @@ struct DevDof {
   int32_t pad;
 };
 
+// A registered inertia ("mass") parameter (nbl_set_inertia_params): read by k_bwd_inertia (inertia_backward.hip) and by
+// idInertiaVjpWorld (dynamics_dev.hpp).
+struct DevInertiaParam {
+  int32_t body, pad;
+  double dG[21];   // d(spatial inertia of `body`)/d(parameter), packed symmetric like DevBody::G
+};
+
 struct DevModel {
   int32_t nb, n, nAction, pad;   // pad: worlds packed into one wavefront of the lane = body tree kernels (>= 1)
   int32_t maxLevel, maxRank, nbp, nFree;  // tree depth, max sibling rank, bodies padded, free-joint bodies (coop tree kernels)

@@ -2045,6 +2045,57 @@ int32_t nbl_forward_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k,
   return NBL_OK;
 }
 
+// ---- gradients of the dynamics calls to the registered inertia parameters (k_inverse_dynamics_inertia_vjp; csrc/dynamics.hip) ------------
+// The table is the one nbl_set_inertia_params[_on] uploaded; none registered: nothing to write, success.
+int32_t nbl_inverse_dynamics_backward_inertia(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
+                                              const double* grad_tau, double* grad_params, int32_t accumulate, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  int32_t rc = dynCheck(m, B, state, grad_tau, workspace, workspace_bytes);
+  if (rc == NBL_OK) rc = dynFlags(flags);
+  if (rc != NBL_OK || B == 0 || m->nParams == 0) return rc;
+  if (!grad_params) return fail(NBL_E_BADARG, "null grad_params for " + std::to_string(m->nParams) + " registered inertia parameters");
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_inverse_dynamics_inertia_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, m->mdl, (int)flags, B, state, accel, grad_tau, (const DevInertiaParam*)m->dParams, m->nParams,
+                     grad_params, accumulate ? 1 : 0, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+// Two launches like nbl_forward_dynamics[_wrench]_backward: a again and -lambda = -M^-1 grad_accel, then the inertia contraction at
+// (q, v, a) with the cotangent -lambda on the same tree slots.
+int32_t nbl_forward_dynamics_backward_inertia(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                              const double* wrench, int32_t flags, const double* grad_accel, double* grad_params,
+                                              int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  int32_t rc;
+  if (k) {
+    rc = wrenchCheck(m, k, B, state, grad_accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
+  } else {
+    rc = fdynCheck(m, B, state, grad_accel, workspace, workspace_bytes);
+    if (rc == NBL_OK) rc = dynFlags(flags);
+  }
+  if (rc != NBL_OK || B == 0 || m->nParams == 0) return rc;
+  if (!grad_params) return fail(NBL_E_BADARG, "null grad_params for " + std::to_string(m->nParams) + " registered inertia parameters");
+  DeviceGuard guard(m->device);
+  double* ws = (double*)workspace;
+  double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
+  double* neglam = accel + (size_t)m->n * (size_t)B;
+  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
+  if (k)
+    hipLaunchKernelGGL(k_forward_dynamics_wrench_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
+                       (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, grad_accel, accel, neglam,
+                       (double*)nullptr, 0, ws);
+  else
+    hipLaunchKernelGGL(k_forward_dynamics_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
+                       m->mdl, (int)flags, B, state, tau, grad_accel, accel, neglam, (double*)nullptr, 0, ws);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_inverse_dynamics_inertia_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, m->mdl,
+                     (int)(flags & DYN_FLAG_MASK), B, state, (const double*)accel, (const double*)neglam, (const DevInertiaParam*)m->dParams,
+                     m->nParams, grad_params, accumulate ? 1 : 0, ws);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
 int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
                                      const double* wrench_guess, int32_t mode, int32_t flags, double* wrench_out, double* tau, void* workspace,
                                      size_t workspace_bytes, void* stream) {

@@ -115,7 +115,11 @@
   int32_t nbl_sensors_forward##S(void*, const void*, int64_t, const double*, const double*, const double*, double*, double*, double*,      \
                                  void*, size_t, void*);                                                                                    \
   int32_t nbl_sensors_backward##S(void*, const void*, int64_t, const double*, const double*, const double*, const double*, const double*,  \
-                                  const double*, double*, double*, double*, int32_t, void*, size_t, void*);
+                                  const double*, double*, double*, double*, int32_t, void*, size_t, void*);                                \
+  int32_t nbl_inverse_dynamics_backward_inertia##S(void*, int64_t, const double*, const double*, int32_t, const double*, double*, int32_t, \
+                                                   void*, size_t, void*);                                                                  \
+  int32_t nbl_forward_dynamics_backward_inertia##S(void*, const void*, int64_t, const double*, const double*, const double*, int32_t,      \
+                                                   const double*, double*, int32_t, void*, size_t, void*);
 
 extern "C" {
 NBL_DECLARE_VARIANT(_c8)
@@ -201,6 +205,8 @@ struct Variant {
   size_t (*sensors_workspace_bytes)(const void*, int64_t);
   int32_t (*sensors_forward)(void*, const void*, int64_t, const double*, const double*, const double*, double*, double*, double*, void*, size_t, void*);
   int32_t (*sensors_backward)(void*, const void*, int64_t, const double*, const double*, const double*, const double*, const double*, const double*, double*, double*, double*, int32_t, void*, size_t, void*);
+  int32_t (*inverse_dynamics_backward_inertia)(void*, int64_t, const double*, const double*, int32_t, const double*, double*, int32_t, void*, size_t, void*);
+  int32_t (*forward_dynamics_backward_inertia)(void*, const void*, int64_t, const double*, const double*, const double*, int32_t, const double*, double*, int32_t, void*, size_t, void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
   {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
@@ -219,7 +225,8 @@ struct Variant {
    nbl_contact_inverse_dynamics##S, nbl_contact_readout##S, nbl_contact_readout_rows##S, nbl_contact_body_wrenches##S,       \
    nbl_body_set_create##S, nbl_body_set_destroy##S, nbl_body_set_mass##S, nbl_body_set_origin_moments##S,         \
    nbl_centroidal_workspace_bytes##S, nbl_centroidal_forward##S, nbl_centroidal_backward##S,                         \
-   nbl_sensors_workspace_bytes##S, nbl_sensors_forward##S, nbl_sensors_backward##S}
+   nbl_sensors_workspace_bytes##S, nbl_sensors_forward##S, nbl_sensors_backward##S,                                  \
+   nbl_inverse_dynamics_backward_inertia##S, nbl_forward_dynamics_backward_inertia##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -520,6 +527,19 @@ int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t
   NBL_WRENCH_MAP_CHECK(m, k);
   return NBL_FWD(m, contact_inverse_dynamics, k ? k->impl : nullptr, B, state, accel, wrench_guess, mode, flags, wrench_out, tau, workspace,
                  workspace_bytes, stream);
+}
+
+int32_t nbl_inverse_dynamics_backward_inertia(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
+                                              const double* grad_tau, double* grad_params, int32_t accumulate, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  return NBL_FWD(m, inverse_dynamics_backward_inertia, B, state, accel, flags, grad_tau, grad_params, accumulate, workspace, workspace_bytes, stream);
+}
+int32_t nbl_forward_dynamics_backward_inertia(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
+                                              const double* wrench, int32_t flags, const double* grad_accel, double* grad_params,
+                                              int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  NBL_WRENCH_MAP_CHECK(m, k);
+  return NBL_FWD(m, forward_dynamics_backward_inertia, k ? k->impl : nullptr, B, state, tau, wrench, flags, grad_accel, grad_params, accumulate,
+                 workspace, workspace_bytes, stream);
 }
 
 int32_t nbl_contact_readout(nbl_model* m, int64_t B, const void* saved, int32_t* count, int32_t* n_limit_rows, int32_t* n_friction_rows,

@@ -39,6 +39,13 @@ a = M^-1 (tau + sum_e J_e^T W_e - C), with exact gradients to the state, accel /
 `contact_inverse_dynamics` (Skeleton::getContactInverseDynamics / getMultipleContactInverseDynamics, Skeleton.cpp:9705-9949; no autograd,
 like the reference) and `inverse_dynamics_from_predictions` (Skeleton::getInverseDynamicsFromPredictions, Skeleton.cpp:9671-9697).
 Out of scope: the ...NearCoP and ...OverTime variants of the contact solve, and gradients through it.
+
+Inertia parameters: the six functions at the top take `mass=` (a 1-D tensor of world.getMassDims() entries, the contract of
+timestep(..., mass=): world.setMasses(mass), and `mass` receives its gradient summed over all worlds), in closed form - inverse dynamics
+is linear in every body's spatial inertia, forward dynamics is its inverse function.  Per world and without autograd:
+`inverse_dynamics_mass_gradient`, `forward_dynamics_mass_gradient` ([..., massDims]) and `inverse_dynamics_mass_jacobian`,
+`forward_dynamics_mass_jacobian` ([..., n, massDims]; Skeleton::getJacobianOfID / getJacobianOfFD with the mass vector as WithRespectTo,
+Skeleton.hpp:650-718).
 """
 from __future__ import annotations
 
@@ -563,44 +570,257 @@ def _wrench_flags(joint_forces: bool, world_frame: bool) -> int:
     return (ID_JOINT_FORCES if joint_forces else 0) | (WRENCH_WORLD if world_frame else 0)
 
 
+# ---- gradients to the registered inertia ("mass") parameters (World.tuneMass / setMasses) ----------------------------------------------------
+# Inverse dynamics is linear in every body's spatial inertia: d(g^T tau) / d theta_p = Fb_i . (dG_p A_i) - ad(V_i, Fb_i) . (dG_p V_i), one
+# root -> leaf sweep and one contraction per parameter (k_inverse_dynamics_inertia_vjp); forward dynamics is its inverse function,
+# d a / d theta = -M^-1 d ID / d theta at (q, v, a).  Skeleton::getJacobianOfID / C / M / Minv / FD with the mass vector as WithRespectTo
+# (Skeleton.hpp:650-718), which the reference finite-differences.
+def _mass_dims(world, what: str) -> int:
+    d = world.getMassDims()
+    if d == 0:
+        raise ValueError(f"{what}: no mass parameters are registered on this world (World.tuneMass)")
+    return d
+
+
+def _set_mass(world, mass, what: str):
+    """the contract of timestep(..., mass=): world.setMasses(mass)"""
+    if not torch.is_tensor(mass) or mass.dim() != 1 or mass.shape[0] != world.getMassDims():
+        raise ValueError(f"mass must be a 1-D tensor of world.getMassDims() = {world.getMassDims()} entries")
+    _mass_dims(world, what)
+    world.setMasses(mass)
+
+
+def inverse_dynamics_inertia_vjp_soa(world, s_soa: torch.Tensor, a_soa, g_soa: torch.Tensor, flags: int = 0, out=None) -> torch.Tensor:
+    """[massDims][B] = (out given: +=) (d tau / d theta)^T g per world, raw SoA like inverse_dynamics_vjp_soa"""
+    B, P = s_soa.shape[1], _mass_dims(world, "inverse_dynamics_inertia_vjp_soa")
+    gm = out if out is not None else torch.empty((P, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        ws = _workspace(world, B)
+        check(world._L.nbl_inverse_dynamics_backward_inertia(world._h, B, _ptr(s_soa), _ptr(a_soa), flags, _ptr(g_soa), _ptr(gm),
+                                                             1 if out is not None else 0, _ptr(ws), ws.numel(), world._stream()),
+              "nbl_inverse_dynamics_backward_inertia")
+    return gm
+
+
+def forward_dynamics_inertia_vjp_soa(world, mapping, s_soa: torch.Tensor, t_soa, w_soa, g_soa: torch.Tensor, flags: int = 0, out=None) -> torch.Tensor:
+    """[massDims][B] = (out given: +=) (d a / d theta)^T g per world; mapping / w_soa None: no wrenches"""
+    B, P = s_soa.shape[1], _mass_dims(world, "forward_dynamics_inertia_vjp_soa")
+    gm = out if out is not None else torch.empty((P, B), dtype=torch.float64, device=world.device)
+    if B > 0:
+        km = _km(world, mapping)
+        ws = _wr_workspace(world, km, B) if km is not None else _fd_workspace(world, B)
+        if km is None:
+            flags &= ~WRENCH_WORLD                                # a frame for wrenches that are not there
+        check(world._L.nbl_forward_dynamics_backward_inertia(world._h, km, B, _ptr(s_soa), _ptr(t_soa), _ptr(w_soa) if km is not None else None, flags,
+                                                             _ptr(g_soa), _ptr(gm), 1 if out is not None else 0, _ptr(ws), ws.numel(), world._stream()),
+              "nbl_forward_dynamics_backward_inertia")
+    return gm
+
+
+def _dyn_inputs(world, what: str, state, x=None, xname: str = "accel"):
+    """(state [2n][B], x [n][B] or None, the leading shape) of `state` [..., 2n] and x [..., n] (the reference's layout allowed)"""
+    _join_if_deferred(world)
+    n = world.n
+    s, _, _ = _restrict(world, state.detach(), what, "state")
+    lead = tuple(s.shape[:-1])
+    s_soa = world.to_soa(world._prep(s.reshape(-1, 2 * n), 2 * n, "dyn_state"))
+    return s_soa, (None if x is None else _vec_soa(world, what, x, xname, lead, "dyn_accel")), lead
+
+
+def _vec_soa(world, what: str, x, xname: str, lead, role: str):
+    n = world.n
+    xr, _, _ = _restrict(world, x.detach(), what, xname)
+    if tuple(xr.shape[:-1]) != lead:
+        raise ValueError(f"{what}: {xname} has leading shape {tuple(xr.shape[:-1])}, state {lead}")
+    return world.to_soa(world._prep(xr.reshape(-1, n), n, role))
+
+
+def _per_world(world, gm: torch.Tensor, lead, like_device):
+    """[massDims][B] -> [..., massDims] where the state came from"""
+    return _give(world, world.from_soa(gm).reshape(lead + (gm.shape[0],)), like_device)
+
+
+def inverse_dynamics_mass_gradient(world, state: torch.Tensor, accel, grad_tau: torch.Tensor, joint_forces: bool = False) -> torch.Tensor:
+    """(d tau / d mass)^T grad_tau of inverse_dynamics(world, state, accel) PER WORLD: [..., massDims], at the World's current masses; no
+    autograd.  accel None: of coriolis_and_gravity.  Wrenches on bodies and the joint forces do not depend on the inertias: the result
+    serves inverse_dynamics(..., wrenches=) unchanged."""
+    what = "inverse_dynamics_mass_gradient"
+    _mass_dims(world, what)
+    s_soa, a_soa, lead = _dyn_inputs(world, what, state, accel)
+    g_soa = _vec_soa(world, what, grad_tau, "grad_tau", lead, "dyn_cot")
+    return _per_world(world, inverse_dynamics_inertia_vjp_soa(world, s_soa, a_soa, g_soa, ID_JOINT_FORCES if joint_forces else 0), lead, state.device)
+
+
+def forward_dynamics_mass_gradient(world, state: torch.Tensor, tau, grad_accel: torch.Tensor, joint_forces: bool = False, wrenches=None,
+                                   bodies=None, world_frame: bool = False) -> torch.Tensor:
+    """(d a / d mass)^T grad_accel of forward_dynamics(world, state, tau[, wrenches ...]) PER WORLD: [..., massDims]; no autograd."""
+    what = "forward_dynamics_mass_gradient"
+    _mass_dims(world, what)
+    s_soa, t_soa, lead = _dyn_inputs(world, what, state, tau, "tau")
+    g_soa = _vec_soa(world, what, grad_accel, "grad_accel", lead, "dyn_cot")
+    mapping = w_soa = None
+    if wrenches is not None:
+        mapping = wrench_set(world, bodies)
+        w_soa = _wrench_inputs(world, what, mapping, wrenches, lead)
+    gm = forward_dynamics_inertia_vjp_soa(world, mapping, s_soa, t_soa, w_soa, g_soa, _wrench_flags(joint_forces, world_frame and wrenches is not None))
+    return _per_world(world, gm, lead, state.device)
+
+
+def _mass_jacobian(world, call, s_soa: torch.Tensor, x_soa, lead, like_device) -> torch.Tensor:
+    """[..., n, massDims]: call(states, x, cotangents) over n x B worlds with the unit cotangents e_i (world i * B + b), cut into launches of
+    whole rows above MASS_BACKWARD_WORLDS"""
+    n, B, P = world.n, s_soa.shape[1], world.getMassDims()
+    per = max(1, min(n, MASS_BACKWARD_WORLDS // max(B, 1)))
+    eye_n = torch.eye(n, dtype=torch.float64, device=world.device)
+    J = torch.empty((P, n, B), dtype=torch.float64, device=world.device)
+    for i0 in range(0, n, per):
+        i1 = min(n, i0 + per)
+        k = i1 - i0
+        J[:, i0:i1] = call(s_soa.repeat(1, k), None if x_soa is None else x_soa.repeat(1, k), eye_n[:, i0:i1].repeat_interleave(B, dim=1).contiguous()).reshape(P, k, B)
+    return _give(world, J.permute(2, 1, 0).reshape(lead + (n, P)).contiguous(), like_device)
+
+
+def inverse_dynamics_mass_jacobian(world, state: torch.Tensor, accel, joint_forces: bool = False) -> torch.Tensor:
+    """d tau / d mass of inverse_dynamics(world, state, accel): [..., n, massDims] - the dynamics regressor restricted to the registered
+    parameters (Skeleton::getJacobianOfID wrt the mass vector; accel None: getJacobianOfC).  One launch over n x B worlds.
+    joint_forces is taken for symmetry with inverse_dynamics and changes nothing: those forces do not depend on the inertias."""
+    what = "inverse_dynamics_mass_jacobian"
+    _mass_dims(world, what)
+    s_soa, a_soa, lead = _dyn_inputs(world, what, state, accel)
+    fl = ID_JOINT_FORCES if joint_forces else 0
+    return _mass_jacobian(world, lambda s, a, g: inverse_dynamics_inertia_vjp_soa(world, s, a, g, fl), s_soa, a_soa, lead, state.device)
+
+
+def forward_dynamics_mass_jacobian(world, state: torch.Tensor, tau, joint_forces: bool = False) -> torch.Tensor:
+    """d a / d mass of forward_dynamics(world, state, tau): [..., n, massDims] (Skeleton::getJacobianOfFD wrt the mass vector).
+    joint_forces: of forward_dynamics(..., joint_forces=True) - the damping and spring forces change a, and with it the Jacobian."""
+    what = "forward_dynamics_mass_jacobian"
+    _mass_dims(world, what)
+    s_soa, t_soa, lead = _dyn_inputs(world, what, state, tau, "tau")
+    fl = ID_JOINT_FORCES if joint_forces else 0
+    return _mass_jacobian(world, lambda s, t, g: forward_dynamics_inertia_vjp_soa(world, None, s, t, None, g, fl), s_soa, t_soa, lead, state.device)
+
+
+class _MassTap(torch.autograd.Function):
+    """Hands `out` on unchanged and gives `mass` its gradient: the layers above stay the functions they are - with and without mass=
+    their outputs and their other gradients are the same bits.  pull(grad_out) -> [massDims], summed over the worlds.
+    The backward passes read the World's CURRENT masses (World.setMasses): this node puts the forward pass's masses back if they were
+    changed in between (an unchanged vector costs nothing), so the gradients of one call are those of one mass vector whatever happened
+    to the World after the forward pass.  It runs before the backward nodes of the layer it wraps because autograd reaches them only
+    through it (its input is their output).  Documented on the public functions (`mass:`)."""
+
+    @staticmethod
+    def forward(ctx, out, mass, pull, world):
+        ctx.pull, ctx.mass_device, ctx.world, ctx.mass_value = pull, mass.device, world, mass.detach().clone()
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ctx.world.setMasses(ctx.mass_value)
+        d_mass = ctx.pull(grad_out.detach()).to(ctx.mass_device) if ctx.needs_input_grad[1] else None
+        return grad_out, d_mass, None, None
+
+
+def _columns_mass_grad(world, s_soa: torch.Tensor, Y: torch.Tensor, Cot: torch.Tensor) -> torch.Tensor:
+    """sum_r (d (M y_r) / d theta)^T cot_r, [massDims, B], of Y, Cot [R, n, B]: the inertia kernel over R x B worlds (world (r, b): a = y_r,
+    no velocity, no gravity), cut into launches of whole right-hand sides like _minv_grad_q"""
+    R, n, B = Y.shape
+    per = max(1, min(R, MASS_BACKWARD_WORLDS // max(B, 1)))
+    gm = torch.zeros((world.getMassDims(), B), dtype=torch.float64, device=world.device)
+    for r0 in range(0, R, per):
+        r1 = min(R, r0 + per)
+        acc = Y[r0:r1].permute(1, 0, 2).reshape(n, (r1 - r0) * B).contiguous()
+        cot = Cot[r0:r1].permute(1, 0, 2).reshape(n, (r1 - r0) * B).contiguous()
+        part = inverse_dynamics_inertia_vjp_soa(world, s_soa.repeat(1, r1 - r0), acc, cot, ID_NO_VELOCITY | ID_NO_GRAVITY).reshape(-1, r1 - r0, B)
+        for r in range(r1 - r0):                                  # summed one by one: the bits do not depend on the chunking
+            gm += part[:, r]
+    return gm
+
+
+def _square_soa(world, G: torch.Tensor, ref: bool, B: int) -> torch.Tensor:
+    """a cotangent [..., n, n] (the reference's layout: its mobile rows and columns) -> [B, n, n] on the World's device"""
+    G = G.to(device=world.device, dtype=torch.float64)
+    if ref:
+        ix = world.ref_layout._idx(world.device, "mobile")
+        G = G.index_select(-1, ix).index_select(-2, ix)
+    return G.reshape(B, world.n, world.n)
+
+
 def inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, joint_forces: bool = False, wrenches=None, bodies=None,
-                     world_frame: bool = False) -> torch.Tensor:
+                     world_frame: bool = False, mass=None) -> torch.Tensor:
     """tau = M(q) a + C(q, v) of `state` = [q; v] ([..., 2n]) and `accel` ([..., n]) -> [..., n]; differentiable in both (exactly).
     joint_forces: + damping v + spring (q - rest + dt v), so that tau applied in timestep() reproduces accel.
     wrenches ([..., 6 E], [torque; force] per entry of `bodies`: an IKMapping of spatial entries, or body names / indices): tau also carries
     - sum_e J_e^T W_e, the wrenches expressed in their entry's frame and acting at its origin (BodyNode::setExtWrench), or with
-    world_frame in world coordinates at that origin; differentiable in the wrenches too.  Without `wrenches` the call is what it was."""
+    world_frame in world coordinates at that origin; differentiable in the wrenches too.  Without `wrenches` the call is what it was.
+    mass (a 1-D tensor of world.getMassDims() entries, the contract of timestep(..., mass=)): world.setMasses(mass) first, and `mass`
+    receives its gradient summed over all worlds; without it the call is what it was.  The backward pass of a call with mass= begins by
+    calling world.setMasses with the forward pass's vector again: if the World's masses were changed in between, backward() resets them
+    (all gradients of the call are then those of one mass vector; an unchanged vector costs nothing)."""
+    if mass is not None:
+        _set_mass(world, mass, "inverse_dynamics")
     if wrenches is None:
         if bodies is not None or world_frame:
             raise ValueError("inverse_dynamics: `bodies` / `world_frame` describe `wrenches`, which were not given")
-        return InverseDynamicsLayer.apply(world, state, accel, ID_JOINT_FORCES if joint_forces else 0)
-    return _WrenchLayer.apply(world, state, accel, wrenches, wrench_set(world, bodies), _wrench_flags(joint_forces, world_frame), False)
+        out = InverseDynamicsLayer.apply(world, state, accel, ID_JOINT_FORCES if joint_forces else 0)
+    else:
+        out = _WrenchLayer.apply(world, state, accel, wrenches, wrench_set(world, bodies), _wrench_flags(joint_forces, world_frame), False)
+    if mass is None:
+        return out
+    return _MassTap.apply(out, mass, lambda g: inverse_dynamics_mass_gradient(world, state, accel, g, joint_forces).reshape(-1, mass.shape[0]).sum(0), world)
 
 
-def coriolis_and_gravity(world, state: torch.Tensor) -> torch.Tensor:
-    """C(q, v): Coriolis, centrifugal and gravity forces of `state` ([..., 2n] -> [..., n]) = inverse_dynamics with a = 0."""
-    return InverseDynamicsLayer.apply(world, state, None, 0)
+def coriolis_and_gravity(world, state: torch.Tensor, mass=None) -> torch.Tensor:
+    """C(q, v): Coriolis, centrifugal and gravity forces of `state` ([..., 2n] -> [..., n]) = inverse_dynamics with a = 0.  mass: as there."""
+    if mass is None:
+        return InverseDynamicsLayer.apply(world, state, None, 0)
+    _set_mass(world, mass, "coriolis_and_gravity")
+    out = InverseDynamicsLayer.apply(world, state, None, 0)
+    return _MassTap.apply(out, mass, lambda g: inverse_dynamics_mass_gradient(world, state, None, g).reshape(-1, mass.shape[0]).sum(0), world)
 
 
-def mass_matrix(world, state: torch.Tensor) -> torch.Tensor:
-    """M(q) of `state` ([..., 2n] -> [..., n, n]; only the positions are read), exactly symmetric; differentiable in the positions."""
-    return MassMatrixLayer.apply(world, state)
+def mass_matrix(world, state: torch.Tensor, mass=None) -> torch.Tensor:
+    """M(q) of `state` ([..., 2n] -> [..., n, n]; only the positions are read), exactly symmetric; differentiable in the positions.
+    mass: as in inverse_dynamics; its gradient is one launch of the inertia kernel over n x B worlds (world (j, b): a = e_j, cotangent
+    G[b, :, j], no velocity, no gravity), the way the position gradient is obtained."""
+    if mass is None:
+        return MassMatrixLayer.apply(world, state)
+    _set_mass(world, mass, "mass_matrix")
+    out = MassMatrixLayer.apply(world, state)
+
+    def pull(G):
+        s_soa, _, _ = _dyn_inputs(world, "mass_matrix", state)
+        n, B = world.n, s_soa.shape[1]
+        Gt = G.to(device=world.device, dtype=torch.float64).reshape(B, n, n).permute(2, 1, 0)              # [j, i, b]: the cotangent of column j
+        eye = torch.eye(n, dtype=torch.float64, device=world.device)[:, :, None].expand(n, n, B)            # [j, i, b]: a = e_j
+        return _columns_mass_grad(world, s_soa, eye, Gt).sum(1)
+    return _MassTap.apply(out, mass, pull, world)
 
 
 def forward_dynamics(world, state: torch.Tensor, tau: torch.Tensor, joint_forces: bool = False, wrenches=None, bodies=None,
-                     world_frame: bool = False) -> torch.Tensor:
+                     world_frame: bool = False, mass=None) -> torch.Tensor:
     """a = M(q)^-1 (tau - C(q, v)) of `state` = [q; v] ([..., 2n]) and `tau` ([..., n]; None: 0) -> [..., n], by the articulated-body
     algorithm; differentiable in both (exactly).  joint_forces: the right-hand side also carries - damping v - spring (q - rest + dt v) as
     the step has it, so that a = (v' - v) / dt of a contact-free timestep() and forward_dynamics inverts inverse_dynamics under the same
     switch.  With a `state` in the reference's layout (immobile skeletons) the result is in that layout too: zero acceleration and zero
     gradient for the frozen coordinates.
     wrenches / bodies / world_frame as in inverse_dynamics: a = M^-1 (tau + sum_e J_e^T W_e - C), its inverse function under equal
-    switches and wrenches; differentiable in the wrenches too.  Without `wrenches` the call is what it was."""
+    switches and wrenches; differentiable in the wrenches too.  Without `wrenches` the call is what it was.
+    mass: as in inverse_dynamics (nbl_forward_dynamics_backward_inertia: d a / d mass = -M^-1 d ID / d mass at (q, v, a))."""
+    if mass is not None:
+        _set_mass(world, mass, "forward_dynamics")
     if wrenches is None:
         if bodies is not None or world_frame:
             raise ValueError("forward_dynamics: `bodies` / `world_frame` describe `wrenches`, which were not given")
-        return ForwardDynamicsLayer.apply(world, state, tau, ID_JOINT_FORCES if joint_forces else 0)
-    return _WrenchLayer.apply(world, state, tau, wrenches, wrench_set(world, bodies), _wrench_flags(joint_forces, world_frame), True)
+        mapping = None
+        out = ForwardDynamicsLayer.apply(world, state, tau, ID_JOINT_FORCES if joint_forces else 0)
+    else:
+        mapping = wrench_set(world, bodies)
+        out = _WrenchLayer.apply(world, state, tau, wrenches, mapping, _wrench_flags(joint_forces, world_frame), True)
+    if mass is None:
+        return out
+    return _MassTap.apply(out, mass, lambda g: forward_dynamics_mass_gradient(world, state, tau, g, joint_forces, None if wrenches is None else wrenches.detach(),
+                                                                              mapping, world_frame).reshape(-1, mass.shape[0]).sum(0), world)
 
 
 def contact_inverse_dynamics(world, state: torch.Tensor, accel: torch.Tensor, bodies, wrench_guesses=None, min_torque: bool = False):
@@ -689,18 +909,49 @@ def inverse_dynamics_from_predictions(world, state: torch.Tensor, accel: torch.T
     return inverse_dynamics(world, state, accel, True, torch.cat(parts, -1), contact, True)
 
 
-def multiply_by_inv_mass_matrix(world, state: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+def multiply_by_inv_mass_matrix(world, state: torch.Tensor, x: torch.Tensor, mass=None) -> torch.Tensor:
     """M(q)^-1 x of `state` ([..., 2n]; only the positions are read) and x = [..., n] or [..., n, R] (R right-hand sides per world: the
     articulated inertias are built once) -> the shape of x.  M is never formed.  Differentiable in x and in the positions (the velocity
-    block receives nothing).  In the reference's layout the frozen coordinates get zeros in the result and in the gradients."""
-    return InvMassApplyLayer.apply(world, state, x)
+    block receives nothing).  In the reference's layout the frozen coordinates get zeros in the result and in the gradients.
+    mass: as in inverse_dynamics; its gradient is -sum_r (d (M y_r) / d mass)^T lambda_r, lambda_r = M^-1 (cotangent of y_r): the inertia
+    kernel over R x B worlds."""
+    if mass is None:
+        return InvMassApplyLayer.apply(world, state, x)
+    _set_mass(world, mass, "multiply_by_inv_mass_matrix")
+    out = InvMassApplyLayer.apply(world, state, x)
+    matrix = x.dim() == state.dim() + 1
+
+    def rhs(t, lead):                                             # [..., n, R] / [..., n] -> [R, n, B]
+        tr = t.detach().transpose(-1, -2) if matrix else t.detach().unsqueeze(-2)
+        tr, _, _ = _restrict(world, tr, "multiply_by_inv_mass_matrix", "x")
+        R = tr.shape[-2]
+        return world._prep(tr.reshape(-1, world.n), world.n, "dyn_rhs").reshape(-1, R, world.n).permute(1, 2, 0).contiguous()
+
+    def pull(g):
+        s_soa, _, lead = _dyn_inputs(world, "multiply_by_inv_mass_matrix", state)
+        Y = inv_mass_apply_soa(world, s_soa, rhs(x, lead))
+        Lam = inv_mass_apply_soa(world, s_soa, rhs(g, lead))
+        return _columns_mass_grad(world, s_soa, Y, -Lam).sum(1)
+    return _MassTap.apply(out, mass, pull, world)
 
 
-def inv_mass_matrix(world, state: torch.Tensor) -> torch.Tensor:
+def inv_mass_matrix(world, state: torch.Tensor, mass=None) -> torch.Tensor:
     """M(q)^-1 of `state` ([..., 2n] -> [..., n, n]), exactly symmetric; differentiable in the positions.  In the reference's layout the
     frozen coordinates have zero rows and columns (the reference's own matrix has the inverse of their blocks there, which a model that
-    welded them to the world cannot give)."""
-    return InvMassMatrixLayer.apply(world, state)
+    welded them to the world cannot give).  mass: as in multiply_by_inv_mass_matrix, with the columns of M^-1 as right-hand sides."""
+    if mass is None:
+        return InvMassMatrixLayer.apply(world, state)
+    _set_mass(world, mass, "inv_mass_matrix")
+    out = InvMassMatrixLayer.apply(world, state)
+
+    def pull(G):
+        s_soa, _, _ = _dyn_inputs(world, "inv_mass_matrix", state)
+        n, B = world.n, s_soa.shape[1]
+        ref = world.ref_layout is not None and G.shape[-1] == world.ref_layout.n_ref and G.shape[-1] != n
+        Y = inv_mass_matrix_soa(world, s_soa).reshape(n, n, B)     # [j][i][b] = Minv[i][j]: the matrix is symmetric bit for bit
+        Lam = inv_mass_apply_soa(world, s_soa, _square_soa(world, G, ref, B).permute(2, 1, 0).contiguous())    # [j, i, b]
+        return _columns_mass_grad(world, s_soa, Y, -Lam).sum(1)
+    return _MassTap.apply(out, mass, pull, world)
 
 
 def _current(world):
@@ -770,3 +1021,81 @@ def world_inv_mass_matrix(world) -> torch.Tensor:
     s = _current(world)
     Mi = world.from_soa(inv_mass_matrix_soa(world, s)).reshape(s.shape[1], world.n, world.n)
     return Mi[0] if getattr(world, "_one_d", False) else Mi
+
+
+# ---- Skeleton::getJacobianOfC / M / ID / Minv / FD on the World's current state (Skeleton.hpp:650-718) ---------------------------------------
+def _wrt_kind(world, wrt) -> str:
+    from .mass import WithRespectToMass
+    from .sensors import WRT_POSITION, WRT_VELOCITY
+    if isinstance(wrt, WithRespectToMass):
+        if wrt is not world.getWrtMass():
+            raise ValueError("the WithRespectToMass of another World")
+        _mass_dims(world, "getJacobianOf...")
+        return "mass"
+    if isinstance(wrt, str) and wrt in (WRT_POSITION, WRT_VELOCITY):
+        return wrt
+    raise NotImplementedError(f"getJacobianOf...: wrt = {wrt!r} is not offered (world.getWrtMass(), neural.WRT_POSITION, neural.WRT_VELOCITY)")
+
+
+def _id_dense(world, s_soa: torch.Tensor, a_soa, flags: int, kind: str) -> torch.Tensor:
+    """[B, n, dim]: d ID(q, v, a) / d wrt under `flags`, rows by unit cotangents: the reverse kernel (positions, velocities) or the inertia
+    kernel (masses) over n x B worlds, cut into launches of whole rows above MASS_BACKWARD_WORLDS"""
+    n, B = world.n, s_soa.shape[1]
+    if kind == "mass":
+        J = _mass_jacobian(world, lambda s, a, g: inverse_dynamics_inertia_vjp_soa(world, s, a, g, flags), s_soa, a_soa, (B,), world.device)
+        return J
+    from .sensors import WRT_POSITION
+    per = max(1, min(n, MASS_BACKWARD_WORLDS // max(B, 1)))
+    eye_n = torch.eye(n, dtype=torch.float64, device=world.device)
+    J = torch.empty((n, n, B), dtype=torch.float64, device=world.device)                 # [column, row i, b]
+    for i0 in range(0, n, per):
+        i1 = min(n, i0 + per)
+        k = i1 - i0
+        gs, _ = inverse_dynamics_vjp_soa(world, s_soa.repeat(1, k), None if a_soa is None else a_soa.repeat(1, k),
+                                         eye_n[:, i0:i1].repeat_interleave(B, dim=1).contiguous(), flags, want_accel=False)
+        J[:, i0:i1] = (gs[:n] if kind == WRT_POSITION else gs[n:]).reshape(n, k, B)
+    return J.permute(2, 1, 0).contiguous()
+
+
+def _fd_dense(world, s_soa: torch.Tensor, t_soa: torch.Tensor, flags: int, kind: str) -> torch.Tensor:
+    """[B, n, dim]: d FD(q, v, tau) / d wrt, rows by unit cotangents through nbl_forward_dynamics_backward[_inertia]"""
+    n, B = world.n, s_soa.shape[1]
+    if kind == "mass":
+        return _mass_jacobian(world, lambda s, t, g: forward_dynamics_inertia_vjp_soa(world, None, s, t, None, g, flags), s_soa, t_soa, (B,), world.device)
+    from .sensors import WRT_POSITION
+    per = max(1, min(n, MASS_BACKWARD_WORLDS // max(B, 1)))
+    eye_n = torch.eye(n, dtype=torch.float64, device=world.device)
+    J = torch.empty((n, n, B), dtype=torch.float64, device=world.device)
+    for i0 in range(0, n, per):
+        i1 = min(n, i0 + per)
+        k = i1 - i0
+        gs, _ = forward_dynamics_vjp_soa(world, s_soa.repeat(1, k), t_soa.repeat(1, k), eye_n[:, i0:i1].repeat_interleave(B, dim=1).contiguous(), flags,
+                                         want_state=True, want_tau=False)
+        J[:, i0:i1] = (gs[:n] if kind == WRT_POSITION else gs[n:]).reshape(n, k, B)
+    return J.permute(2, 1, 0).contiguous()
+
+
+def world_jacobian_of(world, what: str, x, wrt) -> torch.Tensor:
+    """Skeleton::getJacobianOfC / M / ID / Minv / FD (`what` = "C", "M", "ID", "Minv", "FD") on the current state: [B, n, dim(wrt)] on the
+    World's device ([n, dim] for a 1-D state), over the device's (mobile) coordinates, detached."""
+    kind = _wrt_kind(world, wrt)
+    s = _current(world)
+    no_vg = ID_NO_VELOCITY | ID_NO_GRAVITY
+    if what == "C":
+        J = _id_dense(world, s, None, 0, kind)
+    elif what == "M":                                             # d (M x) / d wrt
+        J = _id_dense(world, s, _world_vec(world, x, "getJacobianOfM"), no_vg, kind)
+    elif what == "ID":                                            # d (M x + C) / d wrt
+        J = _id_dense(world, s, _world_vec(world, x, "getJacobianOfID"), 0, kind)
+    elif what == "Minv":                                          # d (M^-1 f) / d wrt = -M^-1 d (M y) / d wrt at y = M^-1 f
+        f = _world_vec(world, x, "getJacobianOfMinv")
+        y = inv_mass_apply_soa(world, s, f.unsqueeze(0))[0]
+        JM = _id_dense(world, s, y, no_vg, kind)                   # [B, n, dim]
+        J = -inv_mass_apply_soa(world, s, JM.permute(2, 1, 0).contiguous()).permute(2, 1, 0).contiguous()
+    else:                                                         # the forward dynamics of the step: the current action's torques, joint forces
+        tau = torch.zeros((world.n, s.shape[1]), dtype=torch.float64, device=world.device)
+        act = getattr(world, "_action", None)
+        if act is not None and act.shape[1] == s.shape[1] and act.shape[0] > 0:
+            tau.index_copy_(0, torch.tensor(world.model.action_map, dtype=torch.long, device=world.device), act)
+        J = _fd_dense(world, s, tau, ID_JOINT_FORCES, kind)
+    return J[0] if getattr(world, "_one_d", False) else J

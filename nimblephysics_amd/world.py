@@ -378,6 +378,35 @@ class World:
         from .dynamics import world_coriolis_and_gravity
         return world_coriolis_and_gravity(self)
 
+    # Skeleton::getJacobianOfC / M / ID / Minv / FD (Skeleton.hpp:650-718) on the current state.  wrt: self.getWrtMass() (the registered
+    # inertia parameters, closed form), neural.WRT_POSITION or neural.WRT_VELOCITY (the dense form of the reverse kernels: n unit
+    # cotangents in one launch); anything else raises NotImplementedError.  [B, n, dim(wrt)] ([n, dim] for a 1-D state), detached.
+    def getJacobianOfC(self, wrt) -> torch.Tensor:
+        """d C(q, v) / d wrt."""
+        from .dynamics import world_jacobian_of
+        return world_jacobian_of(self, "C", None, wrt)
+
+    def getJacobianOfM(self, x, wrt) -> torch.Tensor:
+        """d (M(q) x) / d wrt for x [B, n] ([n])."""
+        from .dynamics import world_jacobian_of
+        return world_jacobian_of(self, "M", x, wrt)
+
+    def getJacobianOfID(self, x, wrt) -> torch.Tensor:
+        """d (M(q) x + C(q, v)) / d wrt: inverse dynamics at the accelerations x."""
+        from .dynamics import world_jacobian_of
+        return world_jacobian_of(self, "ID", x, wrt)
+
+    def getJacobianOfMinv(self, f, wrt) -> torch.Tensor:
+        """d (M(q)^-1 f) / d wrt."""
+        from .dynamics import world_jacobian_of
+        return world_jacobian_of(self, "Minv", f, wrt)
+
+    def getJacobianOfFD(self, wrt) -> torch.Tensor:
+        """d a / d wrt of the forward dynamics the step runs: the torques of the current action (setAction; none: zero) and the joints'
+        damping and spring forces."""
+        from .dynamics import world_jacobian_of
+        return world_jacobian_of(self, "FD", None, wrt)
+
     def getContactInverseDynamics(self, accelerations, body):
         """Skeleton::getContactInverseDynamics on the current state: (contact wrench [B, 6], joint torques [B, n]; [6], [n] for a 1-D
         state) for the accelerations [B, n] ([n]); `body` is a body name or index.  With immobile skeletons the frozen coordinates get zeros."""
