@@ -351,6 +351,9 @@ int32_t nbl_backward_inertia(nbl_model* m, int64_t B, const void* saved, double*
  *     grad_states  [T+1][2n][B]  dL/dstates[t] as it enters the loss directly (zeros where the loss does not look)
  *     grad_state0  [2n][B] out,  grad_actions [T][k][B] out
  * workspace: nbl_rollout_workspace_bytes(m, B) bytes.
+ * Stream semantics: the slices of a rollout fork from `stream` and join into it before the call returns, on every handle.  Deferred
+ * join (nbl_set_deferred_join) does not apply to the rollout entries, these and the checkpointed ones below: on such a handle they
+ * also make `stream` wait for the slices of earlier nbl_step_forward / nbl_step_backward calls before they fork.
  */
 size_t nbl_rollout_workspace_bytes(const nbl_model* m, int64_t B);
 int32_t nbl_rollout_forward(nbl_model* m, int64_t B, int32_t T, const double* state0, const double* actions,
@@ -466,7 +469,13 @@ int32_t nbl_slices_for(const nbl_model* m, int64_t B);
  * can also be consumed on its slice's own stream: nbl_slice_stream gives the stream (a hipStream_t; NULL for slice 0: the calls' own) and the world range
  * [first_world, end_world) of slice `slice` of a call with B worlds - enqueue the per-slice loss there.  The buffers of a call must
  * stay valid until its slices have run.  nbl_slices_for(m, B) is the slice count (4 from 4096 worlds on).  Results are bit for bit
- * those of the joined calls. */
+ * those of the joined calls.
+ * THE MODE COVERS nbl_step_forward AND nbl_step_backward ONLY.  Every other entry behaves on such a handle as on a joined one.  The
+ * rollout entries (nbl_rollout_forward / _backward / _backward_inertia and the _checkpointed pair) first make `stream` wait for the
+ * slices still in flight from earlier step calls (what nbl_join_slices does), then fork their slices from `stream` and join them into
+ * it before they return: inputs produced on `stream` are seen by every slice, results are safe to read on `stream`, and neither
+ * nbl_fork_slices nor nbl_join_slices is needed around them.  The entries that run on `stream` alone (nbl_backward_inertia, the
+ * kinematics, dynamics, sensor and read-out calls) do not look at the slice streams: after deferred step calls, nbl_join_slices first. */
 int32_t nbl_set_deferred_join(nbl_model* m, int32_t enabled);
 int32_t nbl_slice_stream(nbl_model* m, int64_t B, int32_t slice, void** stream, int64_t* first_world, int64_t* end_world);
 int32_t nbl_fork_slices(nbl_model* m, void* stream);

@@ -190,9 +190,10 @@ static int64_t slicePer(int64_t B, int sl) { return (((B + sl - 1) / sl) + 15) &
 // stream wait for them: the slices of
 // consecutive calls - the forward pass of one, the backward pass of another - overlap like the four-handle pattern's, with ONE handle.
 // Whoever consumes a result does so on the slice's stream (nbl_slice_stream) or after nbl_join_slices.
+// `defer` is the CALLER's choice, not the handle's: nbl_step_forward / nbl_step_backward pass m->deferJoin, the rollout entries pass
+// false (a rollout forks from and joins into the caller's stream on every handle; joinDeferredSlices first).
 template <class Fn>
-static int32_t forSlices(nbl_model* m, int64_t B, int sl, hipStream_t s, Fn fn) {
-  const bool defer = m->deferJoin;
+static int32_t forSlices(nbl_model* m, int64_t B, int sl, hipStream_t s, bool defer, Fn fn) {
   if (sl > 1) {
     const int32_t rc = ensureSideStreams(m, sl - 1);
     if (rc != NBL_OK) return rc;
@@ -209,6 +210,16 @@ static int32_t forSlices(nbl_model* m, int64_t B, int sl, hipStream_t s, Fn fn) 
     const int32_t rc = fn(i, b0, b1, st);
     if (rc != NBL_OK) return rc;
     if (i > 0 && !defer) { HIP_TRY(hipEventRecord(m->sideDone[i - 1], st)); HIP_TRY(hipStreamWaitEvent(s, m->sideDone[i - 1], 0)); }
+  }
+  return NBL_OK;
+}
+// `s` waits for everything the handle's slice streams hold (nbl_join_slices).  The rollout entries start with it on a deferred-join
+// handle: slices of earlier nbl_step_forward / nbl_step_backward calls may still be in flight - they may write the rollout's inputs
+// and they use the workspace - and the fork of a joined call orders the slice streams after `s` only.
+static int32_t joinDeferredSlices(nbl_model* m, hipStream_t s) {
+  for (size_t i = 0; i < m->side.size(); i++) {
+    HIP_TRY(hipEventRecord(m->sideDone[i], m->side[i]));
+    HIP_TRY(hipStreamWaitEvent(s, m->sideDone[i], 0));
   }
   return NBL_OK;
 }
@@ -886,7 +897,7 @@ int32_t nbl_step_forward(nbl_model* m, int64_t B, const double* state, const dou
   if (B <= 0) return fail(NBL_E_BADARG, "B must be positive");
   if (workspace_bytes < nbl_workspace_bytes(m, B)) return fail(NBL_E_WORKSPACE, "workspace too small");
   m->timingNow = m->timing && (m->fwdCalls++ % m->timingPeriod == 0);
-  const int32_t rc = forSlices(m, B, slicesFor(m, B), (hipStream_t)stream, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
+  const int32_t rc = forSlices(m, B, slicesFor(m, B), (hipStream_t)stream, m->deferJoin, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
     return launchForward(m, B, si, b0, b1, s, state, action, lcp_cache_in, next_state, lcp_cache_out, saved, status, workspace);
   });
   if (rc != NBL_OK) return rc;
@@ -999,7 +1010,7 @@ int32_t nbl_step_backward(nbl_model* m, int64_t B, const void* saved, const doub
   if (B <= 0) return fail(NBL_E_BADARG, "B must be positive");
   if (workspace_bytes < nbl_workspace_bytes(m, B)) return fail(NBL_E_WORKSPACE, "workspace too small");
   m->timingNow = m->timing && (m->bwdCalls++ % m->timingPeriod == 0);
-  const int32_t rc = forSlices(m, B, slicesFor(m, B), (hipStream_t)stream, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
+  const int32_t rc = forSlices(m, B, slicesFor(m, B), (hipStream_t)stream, m->deferJoin, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
     return launchBackward(m, B, si, b0, b1, s, saved, grad_next_state, grad_state, grad_action, workspace);
   });
   if (rc != NBL_OK) return rc;
@@ -1494,10 +1505,11 @@ int32_t nbl_rollout_forward_checkpointed(nbl_model* m, int64_t B, int32_t T, int
   if (segment > 0 && m->hasContact && warm_start && !checkpoints) return fail(NBL_E_BADARG, "a checkpointed warm-started rollout needs the checkpoint buffer");
   hipStream_t s0 = (hipStream_t)stream;
   const RolloutBufs r = rolloutBufs(m, B, T, segment, actions, action_stride, states, saved, checkpoints, status, warm_start, workspace);
+  if (m->deferJoin) { const int32_t rj = joinDeferredSlices(m, s0); if (rj != NBL_OK) return rj; }   // a rollout is a joined call on every handle
   HIP_TRY(hipMemcpyAsync(states, state0, r.stateElems * sizeof(double), hipMemcpyDeviceToDevice, s0));
   m->timingNow = false;
   // slice-major: every slice runs its T steps on its own stream; the slices only join at the end
-  const int32_t rc = forSlices(m, B, rolloutSlicesFor(m, B), s0, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
+  const int32_t rc = forSlices(m, B, rolloutSlicesFor(m, B), s0, false, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
     return rolloutStepsOfSlice(m, B, si, b0, b1, s, r, 0, T, false, workspace);
   });
   if (rc != NBL_OK) return rc;
@@ -1542,7 +1554,8 @@ int32_t nbl_rollout_backward_checkpointed(nbl_model* m, int64_t B, int32_t T, in
   const int rows = 2 * m->n;
   const int32_t seg = segment > 0 ? segment : T, nSeg = (T + seg - 1) / seg;
   m->timingNow = false;
-  const int32_t rc = forSlices(m, B, rolloutSlicesFor(m, B), s0, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
+  if (m->deferJoin) { const int32_t rj = joinDeferredSlices(m, s0); if (rj != NBL_OK) return rj; }   // (as in the forward call)
+  const int32_t rc = forSlices(m, B, rolloutSlicesFor(m, B), s0, false, [&](int si, int64_t b0, int64_t b1, hipStream_t s) -> int32_t {
     const unsigned blocks = (unsigned)(((b1 - b0) * rows + 255) / 256), cblocks = (unsigned)(((b1 - b0) * (MAX_ROWS + 1) + 255) / 256);
     hipLaunchKernelGGL(k_copy_rows, dim3(blocks), dim3(256), 0, s, g, grad_states + (size_t)T * r.stateElems, B, b0, b1, rows);
     for (int32_t k = nSeg - 1; k >= 0; k--) {
@@ -1624,11 +1637,7 @@ int32_t nbl_fork_slices(nbl_model* m, void* stream) {
 }
 int32_t nbl_join_slices(nbl_model* m, void* stream) {
   if (!m) return fail(NBL_E_BADARG, "null model");
-  for (size_t i = 0; i < m->side.size(); i++) {
-    HIP_TRY(hipEventRecord(m->sideDone[i], m->side[i]));
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, m->sideDone[i], 0));
-  }
-  return NBL_OK;
+  return joinDeferredSlices(m, (hipStream_t)stream);
 }
 
 int32_t nbl_set_launch_lanes(nbl_model* m, int32_t tree_lanes, int32_t lcp_lanes) {

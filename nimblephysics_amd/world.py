@@ -12,6 +12,7 @@ Differences, all forced by batching:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence
 
@@ -22,6 +23,7 @@ from .ref_layout import RefLayout
 
 from . import _abi
 from ._lib import NimbleAmdError, check, lib
+from .mapping import _join_if_deferred
 from .mass import WithRespectToMass, WrtMassBodyNodeEntryType
 from .model import ModelDescription
 
@@ -73,6 +75,7 @@ class World:
         self.ref_layout = RefLayout(mob) if mob is not None and not all(mob) else None
         self._ref_action_map = list(range(self.ref_layout.n_ref)) if self.ref_layout is not None else None
         self._ref_state_like = None
+        self._deferred = False   # set_deferred_join: a mode of this World, re-applied to every handle it creates (_create_handle)
         self._create_handle()
         if self.ref_layout is not None and self.ref_layout.n_dev != self.n:
             raise NimbleAmdError(f"the reference layout names {self.ref_layout.n_dev} mobile coordinates, the model has {self.n}")
@@ -95,6 +98,8 @@ class World:
         self._ws, self._ws_B, self._scratch_saved = None, 0, None
         self._last_record = None
         self._uploaded_inertia = [(float(b.mass), tuple(float(x) for x in b.com), tuple(float(x) for x in b.inertia)) for b in self.model.bodies]
+        if self._deferred:                                 # (setActionSpace, setPositionLimitEnforced, ...: the World stays in its mode)
+            check(self._L.nbl_set_deferred_join(self._h, 1), "nbl_set_deferred_join")
 
     def _destroy_handle(self):
         if getattr(self, "_h", None):
@@ -110,7 +115,8 @@ class World:
 
     def clone(self) -> "World":
         """World::clone (World.cpp:114-172): an independent world with the same model, action space, registered mass parameters
-        and current masses - the reference's unit of concurrency (one clone per thread), here one clone per HIP stream."""
+        and current masses - the reference's unit of concurrency (one clone per thread), here one clone per HIP stream.  The clone has
+        a handle and slice streams of its own and starts with joined calls, whatever set_deferred_join says on this World."""
         w = World(self.description, self.device)       # the description carries the action space and the current masses
         for e in self._wrt_mass.entries:
             w._wrt_mass.registerNode(e.body, e.type, e.upper, e.lower)
@@ -271,6 +277,33 @@ class World:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    @contextlib.contextmanager
+    def _joined_call(self):
+        """Around a library call that is not a deferred entry point (set_deferred_join): on a deferred-join World the current stream
+        first waits for the slices in flight (they may write the call's inputs, and they use the workspace), the slice streams then wait
+        for the current stream (inputs produced there), and the current stream waits for the slices again once the call is enqueued -
+        the call is ordered like one on a joined World.  Nothing on a joined World."""
+        if not self._deferred:
+            yield
+            return
+        self.join()
+        self.fork()
+        try:
+            yield
+        finally:
+            self.join()
+
+    @contextlib.contextmanager
+    def _model_upload(self):
+        """Around a stream-ordered upload of model constants: on a deferred-join World it starts after the slices in flight (they read
+        the constants), and the slice streams wait for it before they run anything else."""
+        _join_if_deferred(self)
+        try:
+            yield
+        finally:
+            if self._deferred:
+                self.fork()
+
     # ---- layout helpers: [B, d] (reference: stack of 1-D vectors) <-> [d][B] ----------------------
     def to_soa(self, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
@@ -328,6 +361,7 @@ class World:
     # ---- state / action API ---------------------------------------------------------------------
     def setState(self, state: torch.Tensor):
         self._one_d = state.dim() == 1                  # one world given as the reference's 1-D vector (neural.forwardPass answers alike)
+        _join_if_deferred(self)                         # (the buffer this replaces may still be read by slices in flight)
         if self.ref_layout is not None:
             full = state.detach()
             self._ref_state_like = (full if full.dim() == 2 else full.unsqueeze(0)).to(device=self.device, dtype=torch.float64).clone()
@@ -335,6 +369,7 @@ class World:
         self._state = self.to_soa(self._prep(state, 2 * self.n, "setState"))
 
     def getState(self) -> torch.Tensor:
+        _join_if_deferred(self)                         # (the state may come out of slices in flight: step_into)
         out = self.from_soa(self._state)
         if self.ref_layout is not None:
             like = self._ref_state_like
@@ -344,6 +379,7 @@ class World:
         return out
 
     def setAction(self, action: torch.Tensor):
+        _join_if_deferred(self)
         if self.ref_layout is not None:
             k_ref = len(self._ref_action_map)
             if action.shape[-1] != k_ref:
@@ -524,8 +560,9 @@ class World:
         ws = self._workspace(B)
         cache_in = self.lcp_cache if (self.lcp_cache is not None and self.lcp_cache.shape == (self.m, B)) else None
         cache_out = torch.empty((self.m, B), dtype=torch.float64, device=self.device) if self.m > 0 else None
-        check(self._L.nbl_step_forward(self._h, B, _ptr(state), _ptr(action), _ptr(cache_in), _ptr(nxt), _ptr(cache_out),
-                                       _ptr(saved), _ptr(status), _ptr(ws), ws.numel(), self._stream()), "nbl_step_forward")
+        with self._joined_call():
+            check(self._L.nbl_step_forward(self._h, B, _ptr(state), _ptr(action), _ptr(cache_in), _ptr(nxt), _ptr(cache_out),
+                                           _ptr(saved), _ptr(status), _ptr(ws), ws.numel(), self._stream()), "nbl_step_forward")
         if cache_out is not None:
             self.lcp_cache = cache_out
         self.last_status = status
@@ -539,8 +576,9 @@ class World:
         gs = torch.empty_like(grad_next)
         ga = torch.empty((self.k, B), dtype=torch.float64, device=self.device)
         ws = self._workspace(B)
-        check(self._L.nbl_step_backward(self._h, B, _ptr(saved), _ptr(grad_next), _ptr(gs), _ptr(ga), _ptr(ws), ws.numel(),
-                                        self._stream()), "nbl_step_backward")
+        with self._joined_call():
+            check(self._L.nbl_step_backward(self._h, B, _ptr(saved), _ptr(grad_next), _ptr(gs), _ptr(ga), _ptr(ws), ws.numel(),
+                                            self._stream()), "nbl_step_backward")
         return gs, ga
 
     # ---- inertia ("mass") parameters (World.cpp:1014-1053, 1821-1824; WithRespectToMass.cpp) ------------
@@ -587,7 +625,7 @@ class World:
             mass = np.asarray([values[i][0] for i in changed], dtype=np.float64)
             com = np.asarray([values[i][1] for i in changed], dtype=np.float64).reshape(-1, 3)
             ine = np.asarray([values[i][2] for i in changed], dtype=np.float64).reshape(-1, 6)
-            with torch.cuda.device(self.device):
+            with torch.cuda.device(self.device), self._model_upload():
                 check(self._L.nbl_set_body_inertias(self._h, len(changed), idx.ctypes.data_as(C.c_void_p), mass.ctypes.data_as(C.c_void_p),
                                                     com.ctypes.data_as(C.c_void_p), ine.ctypes.data_as(C.c_void_p), self._stream()),
                       "nbl_set_body_inertias")
@@ -602,7 +640,7 @@ class World:
     def _push_inertia_params(self):
         bodies, dG = self._wrt_mass.device_table()
         cnt = int(bodies.shape[0])
-        with torch.cuda.device(self.device):     # stream-ordered like the body constants it belongs to (same stream)
+        with torch.cuda.device(self.device), self._model_upload():     # stream-ordered like the body constants it belongs to (same stream)
             check(self._L.nbl_set_inertia_params_on(self._h, cnt, bodies.ctypes.data_as(C.c_void_p) if cnt else None,
                                                     dG.ctypes.data_as(C.c_void_p) if cnt else None, self._stream()), "nbl_set_inertia_params_on")
 
@@ -615,6 +653,7 @@ class World:
             return torch.zeros((0, B), dtype=torch.float64, device=self.device)
         g = out if out is not None else torch.empty((d, B), dtype=torch.float64, device=self.device)
         ws = self._workspace(B)
+        _join_if_deferred(self)                  # (runs on the current stream alone; the record may come out of backward_into)
         check(self._L.nbl_backward_inertia(self._h, B, _ptr(saved), _ptr(g), 1 if out is not None else 0, _ptr(ws), ws.numel(),
                                            self._stream()), "nbl_backward_inertia")
         return g
@@ -779,9 +818,20 @@ class World:
 
     # ---- deferred join: one handle, slices that are not joined per call (nbl_set_deferred_join, include/nimble_amd.h) ----
     def set_deferred_join(self, enabled: bool = True):
-        """With it on, step_into / backward_into (and step_soa / backward_soa) return while their slices still run on the handle's internal
-        streams; consume a result on its slice's stream (`slices(B)`) or after `join()`.  Buffers handed to a call must outlive it: use
-        the *_into entry points with buffers you keep (torch's caching allocator knows nothing of the internal streams)."""
+        """With it on, step_into / backward_into return while their slices still run on the handle's internal streams; consume a result
+        on its slice's stream (`slices(B)`) or after `join()`, and `fork()` after producing inputs on the current stream.  Buffers handed to
+        a call must outlive it: use the *_into entry points with buffers you keep (torch's caching allocator knows nothing of the
+        internal streams).
+
+        THE RULE: the deferred entry points are step_into, backward_into, slices, join and fork - nothing else.  Every other method of
+        this World that launches work (step_soa / backward_soa and with them timestep(), step(), neural.forwardPass and the dense
+        Jacobian getters; rollout_soa / rollout_backward_soa and with them rollout() and GraphedRollout; backward_inertia_soa; setState /
+        getState / setAction; setMasses; the kinematics, dynamics, centroidal, sensor and contact read-outs) behaves as on a joined World:
+        it waits for the slices still in flight, its inputs may be produced on the current stream right before the call, and what it
+        returns is safe to consume on the current stream right after it.  Turning the mode off joins first.  The mode belongs to this
+        World and survives a re-upload of its model (setActionSpace, ...); a clone() starts with joined calls."""
+        if self._deferred and not enabled:
+            self.join()
         check(self._L.nbl_set_deferred_join(self._h, 1 if enabled else 0), "nbl_set_deferred_join")
         self._deferred = bool(enabled)
 

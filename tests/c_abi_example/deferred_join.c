@@ -3,6 +3,11 @@
  * state, a strided device-to-device copy) is enqueued on the slice's own stream (nbl_slice_stream) - against the same K steps with
  * joined calls.  The two runs must agree BYTE FOR BYTE (next state, status, both gradients, the warm start): the deferred join changes
  * where the work is ordered, not what is computed.  Prints one line: slices, bytes compared, and "identical" or the first difference.
+ * Then a ROLLOUT on the same handle (nbl_rollout_forward + nbl_rollout_backward, RT steps), in both passes: the rollout entries are not
+ * deferred entries (nimble_amd.h) - no nbl_fork_slices before them and no nbl_join_slices after them.  The state0 buffer holds a decoy
+ * (the next state of the steps) until the last operation of a busy producer on `stream` writes the real one, and the results are copied
+ * to the host on `stream` right after the calls: a slice that does not wait for `stream`, or that `stream` does not wait for, shows as
+ * a difference between the passes.
  * (What a cgo / JNI / N-API binding of the reference would do around its own training loop: tests/test_gpu_c_abi.py runs it.) */
 #include <math.h>
 #include <stdio.h>
@@ -17,7 +22,9 @@
 
 static double* dalloc(size_t doubles) { void* p = NULL; return hipMalloc(&p, doubles * sizeof(double)) == hipSuccess ? (double*)p : NULL; }
 
-typedef struct { double *next, *gs, *ga, *cache; uint32_t* status; } Result;
+typedef struct { double *next, *gs, *ga, *cache, *rstates, *rg0, *rga; uint32_t* status; } Result;
+#define RT 4        /* steps of the rollout */
+#define BUSY 200    /* device-to-device copies of one saved record (26.7 kB per world) ahead of the rollout's real state0 */
 
 int main(int argc, char** argv) {
   const int64_t B = argc > 1 ? atoll(argv[1]) : 4096;
@@ -49,6 +56,17 @@ int main(int argc, char** argv) {
   HIP(hipMemcpy(s0, h, nS * sizeof(double), hipMemcpyHostToDevice));
   for (int r = 0; r < k; r++) for (int64_t b = 0; b < B; b++) h[(size_t)r * B + b] = 0.1 * sin((double)b + (double)r);
   HIP(hipMemcpy(act, h, nA * sizeof(double), hipMemcpyHostToDevice));
+  /* the rollout's buffers; its cotangents: a fixed pattern on every state of the trajectory */
+  const size_t rwsBytes = nbl_rollout_workspace_bytes(m, B);
+  double *rs0 = dalloc(nS), *rstates = dalloc((RT + 1) * nS), *rgrad = dalloc((RT + 1) * nS), *rg0 = dalloc(nS), *rga = dalloc(RT * nA);
+  void *rws = NULL, *rsv = NULL, *junk = NULL;
+  uint32_t* rst = NULL;
+  HIP(hipMalloc(&rws, rwsBytes)); HIP(hipMalloc(&rsv, (size_t)RT * svBytes)); HIP(hipMalloc(&junk, svBytes)); HIP(hipMalloc((void**)&rst, (size_t)RT * B * sizeof(uint32_t)));
+  if (!rs0 || !rstates || !rgrad || !rg0 || !rga) { fprintf(stderr, "hipMalloc failed\n"); return 1; }
+  double* hg = (double*)malloc((RT + 1) * nS * sizeof(double));
+  for (size_t i = 0; i < (RT + 1) * nS; i++) hg[i] = cos(0.37 * (double)(i % 1009) + 0.11 * (double)(i / nS));
+  HIP(hipMemcpy(rgrad, hg, (RT + 1) * nS * sizeof(double), hipMemcpyHostToDevice));
+  free(hg);
   hipStream_t stream = NULL;
   HIP(hipStreamCreate(&stream));
   Result res[2];
@@ -79,19 +97,37 @@ int main(int argc, char** argv) {
     HIP(hipMemcpy(r->next, next, nS * sizeof(double), hipMemcpyDeviceToHost)); HIP(hipMemcpy(r->gs, gs, nS * sizeof(double), hipMemcpyDeviceToHost));
     HIP(hipMemcpy(r->ga, ga, nA * sizeof(double), hipMemcpyDeviceToHost)); HIP(hipMemcpy(r->cache, cache, nC * sizeof(double), hipMemcpyDeviceToHost));
     HIP(hipMemcpy(r->status, st, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    /* the rollout: decoy in state0, zeros (finite) in every output, a busy `stream`, the real state0 last - and neither fork nor join */
+    HIP(hipMemcpyAsync(rs0, next, nS * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    HIP(hipMemsetAsync(rstates, 0, (RT + 1) * nS * sizeof(double), stream)); HIP(hipMemsetAsync(rg0, 0, nS * sizeof(double), stream));
+    HIP(hipMemsetAsync(rga, 0, RT * nA * sizeof(double), stream));
+    HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < BUSY; i++) HIP(hipMemcpyAsync(junk, sv, svBytes, hipMemcpyDeviceToDevice, stream));
+    HIP(hipMemcpyAsync(rs0, s0, nS * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    CHECK(nbl_rollout_forward(m, B, RT, rs0, act, 0, rstates, rsv, rst, 1, rws, rwsBytes, stream));      /* one action block for every step */
+    CHECK(nbl_rollout_backward(m, B, RT, rsv, rgrad, rg0, rga, rws, rwsBytes, stream));
+    r->rstates = (double*)malloc((RT + 1) * nS * sizeof(double)); r->rg0 = (double*)malloc(nS * sizeof(double)); r->rga = (double*)malloc(RT * nA * sizeof(double));
+    HIP(hipMemcpyAsync(r->rstates, rstates, (RT + 1) * nS * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP(hipMemcpyAsync(r->rg0, rg0, nS * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP(hipMemcpyAsync(r->rga, rga, RT * nA * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP(hipStreamSynchronize(stream));
   }
   CHECK(nbl_set_deferred_join(m, 0));
   int64_t contact = 0, stage0 = 0, finite = 1;
   for (int64_t b = 0; b < B; b++) { contact += (res[1].status[b] & NBL_ST_CONTACT) != 0; stage0 += (res[1].status[b] & NBL_ST_LCP_STAGE0) != 0; }
-  for (size_t i = 0; i < nS; i++) if (!isfinite(res[1].next[i]) || !isfinite(res[1].gs[i])) finite = 0;
+  for (size_t i = 0; i < nS; i++) if (!isfinite(res[1].next[i]) || !isfinite(res[1].gs[i]) || !isfinite(res[1].rstates[RT * nS + i]) || !isfinite(res[1].rg0[i])) finite = 0;
   const char* what = NULL;
   if (memcmp(res[0].next, res[1].next, nS * sizeof(double))) what = "next state";
   else if (memcmp(res[0].gs, res[1].gs, nS * sizeof(double))) what = "state gradient";
   else if (memcmp(res[0].ga, res[1].ga, nA * sizeof(double))) what = "action gradient";
   else if (memcmp(res[0].cache, res[1].cache, nC * sizeof(double))) what = "warm start";
   else if (memcmp(res[0].status, res[1].status, B * sizeof(uint32_t))) what = "status";
+  else if (memcmp(res[0].rstates, res[1].rstates, (RT + 1) * nS * sizeof(double))) what = "rollout states";
+  else if (memcmp(res[0].rg0, res[1].rg0, nS * sizeof(double))) what = "rollout state gradient";
+  else if (memcmp(res[0].rga, res[1].rga, RT * nA * sizeof(double))) what = "rollout action gradient";
+  else if (memcmp(res[0].rstates + RT * nS, res[0].rstates, nS * sizeof(double)) == 0) what = "rollout did not move";
   printf("worlds %lld steps %d slices %d contact %lld stage0 %lld finite %lld bytes %zu %s%s\n", (long long)B, K, slices, (long long)contact, (long long)stage0,
-         (long long)finite, (2 * nS + nA + nC) * sizeof(double) + B * sizeof(uint32_t), what ? "DIFFERENT: " : "identical", what ? what : "");
+         (long long)finite, (2 * nS + nA + nC + (RT + 2) * nS + RT * nA) * sizeof(double) + B * sizeof(uint32_t), what ? "DIFFERENT: " : "identical", what ? what : "");
   nbl_model_destroy(m);
   return what ? 2 : 0;
 }

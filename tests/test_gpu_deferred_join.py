@@ -56,3 +56,36 @@ def test_deferred_join_equals_the_joined_calls_bit_for_bit():
     nxt, sv, status = w.step_soa(st, at, want_saved=True)
     torch.cuda.synchronize()
     assert torch.equal(nxt, want[0][0]) and torch.equal(status, want[0][1])
+
+
+def test_the_fast_path_is_what_it_was_one_step_forward_backward_join():
+    """step_into, backward_into, join(): the deferred entry points run exactly the joined kernels on their slices - bit for bit the joined
+    World's step_soa / backward_soa, on four slices of 256 worlds and on two uneven ones (513 worlds: 272 + 241).  The calls that are NOT
+    deferred entry points (tests/test_gpu_deferred_join_entries.py) changed around this path, not in it."""
+    import nimblephysics_amd as na
+    dev = torch.device("cuda:0")
+    for B, slices in ((1024, 4), (513, 2)):
+        md, s, a = contact_inputs("atlas20", B, 12, joint_noise=0.02, vel_noise=0.01, action_noise=0.0)
+        ref = na.World(md, device=dev)
+        ref.set_slices(slices)
+        st = ref.to_soa(torch.tensor(s, device=dev)); at = ref.to_soa(torch.tensor(a, device=dev))
+        g = torch.tensor(np.random.default_rng(B).normal(0, 1, (s.shape[1], B)), device=dev)
+        nxt, sv, status = ref.step_soa(st, at, want_saved=True)
+        gs, ga = ref.backward_soa(sv, g)
+        torch.cuda.synchronize()
+
+        w = na.World(md, device=dev)
+        w.set_slices(slices)
+        w.set_deferred_join(True)
+        sl = w.slices(B)
+        assert len(sl) == slices and sl[0][1] == 0 and sl[-1][2] == B and (B % slices == 0 or sl[-1][2] - sl[-1][1] < sl[0][2] - sl[0][1])
+        b = dict(nxt=torch.zeros_like(nxt), saved=torch.empty(w.saved_bytes(B), dtype=torch.uint8, device=dev), status=torch.zeros_like(status),
+                 cache=torch.zeros((w.m, B), dtype=torch.float64, device=dev), gs=torch.zeros_like(gs), ga=torch.zeros_like(ga))
+        w.fork()
+        w.step_into(st, at, b["nxt"], b["saved"], b["status"], None, b["cache"])
+        w.backward_into(b["saved"], g, b["gs"], b["ga"])
+        w.join()
+        torch.cuda.synchronize()
+        assert torch.equal(b["nxt"], nxt) and torch.equal(b["status"], status) and torch.equal(b["cache"], ref.lcp_cache), (B, slices)
+        assert torch.equal(b["gs"], gs) and torch.equal(b["ga"], ga), (B, slices)
+        assert 0 < (status & 0x2).ne(0).float().mean().item() < 1          # some worlds leave LCP stage 0: the cascade ran on part of the batch
