@@ -414,6 +414,17 @@ int32_t nbl_selftest_lcp_dantzig_timed(int32_t count, int32_t n, const double* A
  * Exactly the device code of k_contact_solve_gen; tests/test_gpu_general.py compares it with the same code compiled for the host. */
 int32_t nbl_selftest_lcp_cascade(int32_t count, int32_t m, const double* A, const double* b, const double* mu, int32_t have_cache,
                                  const double* x_cache, const uint8_t* on, double fallback_cfm, double* x, int32_t* cls, uint32_t* st, double* cfm);
+/* The same with the two kinds of joint pseudo-contact a step of the general instantiation carries next to its contacts, per SLOT of three rows
+ * (HOST pointers, each [count][m / 3]; NULL: none - then this is nbl_selftest_lcp_cascade): lim 1 = a joint-limit row ([0, inf), no tangent
+ * rows), 2 = one the step carries negated (the caller hands in the negated row: A_dev = S A S, b_dev = S b, x = S x_dev with S = -1 there);
+ * bound > 0 = a joint Coulomb friction row with the FIXED bounds [-bound, bound] and findex -1 on the slot's first row (b = -qdot of the
+ * DOF), its tangent rows empty; mu of such slots is ignored.  When any bound is > 0 the kernel is the instantiation of models with joint
+ * friction (the JF = true text of genValid, genClassify, genLoadProblem and the stages), otherwise the one nbl_selftest_lcp_cascade runs.
+ * Outputs as there.  For tests (tests/test_gpu_lcp_box_rows.py: against the same code on the host and the reference's isLCPSolutionValid);
+ * added within minor 5. */
+int32_t nbl_selftest_lcp_cascade_rows(int32_t count, int32_t m, const double* A, const double* b, const double* mu, const double* bound,
+                                      const uint8_t* lim, int32_t have_cache, const double* x_cache, const uint8_t* on, double fallback_cfm,
+                                      double* x, int32_t* cls, uint32_t* st, double* cfm);
 
 /* Runs the library's device pseudo-inverses on `count` caller-supplied 24 x 24 matrices (HOST pointers: Q [count][24*24] row-major,
  * rows / columns outside the block of interest zero; cTrue [count] = size of that block, Eigen's `size` in the rank threshold), one

@@ -48,6 +48,7 @@
 #define nbl_selftest_lcp_dantzig NBL_V(nbl_selftest_lcp_dantzig)
 #define nbl_selftest_lcp_dantzig_timed NBL_V(nbl_selftest_lcp_dantzig_timed)
 #define nbl_selftest_lcp_cascade NBL_V(nbl_selftest_lcp_cascade)
+#define nbl_selftest_lcp_cascade_rows NBL_V(nbl_selftest_lcp_cascade_rows)
 #define nbl_selftest_pinv NBL_V(nbl_selftest_pinv)
 #define nbl_selftest_pinv_rows NBL_V(nbl_selftest_pinv_rows)
 #define nbl_selftest_stage0_rows NBL_V(nbl_selftest_stage0_rows)

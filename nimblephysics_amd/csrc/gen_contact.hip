@@ -990,10 +990,14 @@ __global__ __launch_bounds__(64) void k_selftest_dantzig_gen(int count, int n, c
   for (int i = ln; i < n; i += 64) x[pb * n + i] = r == 1 ? P.x[i] : 0.0;
 }
 
-// Self-test of the general solver cascade (nbl_selftest_lcp_cascade): one wavefront per problem, the rows set up like k_contact_solve_gen
-// sets them up (three per contact, mu per contact, optionally a mask of the rows of one constrained group), then genStage0 / genCascade.
+// Self-test of the general solver cascade (nbl_selftest_lcp_cascade, nbl_selftest_lcp_cascade_rows): one wavefront per problem, the rows set
+// up like k_contact_solve_gen sets them up (three per slot, mu per contact, optionally a mask of the rows of one constrained group), then
+// genStage0 / genCascade.  lim [count][m / 3] (NULL: contacts only): 1 = the slot is a joint-limit pseudo-contact, 2 = one carried negated;
+// bound [count][m / 3] (NULL: none): > 0 = the slot is a joint friction row with the fixed bounds [-bound, bound] (JF; genBoxRow).
+template <bool JF>
 __global__ __launch_bounds__(64) void k_selftest_cascade_gen(int count, int m, const double* __restrict__ A, const double* __restrict__ b,
-                                                            const double* __restrict__ mu, int haveCache, const double* __restrict__ xcache,
+                                                            const double* __restrict__ mu, const double* __restrict__ bound,
+                                                            const uint8_t* __restrict__ lim, int haveCache, const double* __restrict__ xcache,
                                                             const uint8_t* __restrict__ on, double fallbackCfm, double* __restrict__ x,
                                                             int32_t* __restrict__ cls, uint32_t* __restrict__ st, double* __restrict__ cfmOut,
                                                             double* __restrict__ gws) {
@@ -1012,24 +1016,32 @@ __global__ __launch_bounds__(64) void k_selftest_cascade_gen(int count, int m, c
   for (int j = ln; j < m; j += 64) for (int i = 0; i < m; i++) Ap[(size_t)i * GR + j] = A[((size_t)pb * m + i) * m + j];
   R.m = m; R.ld = GR;
   w.sync();
+  int nLimMine = 0;
   for (int r = ln; r < m; r += 64) {
-    double mr = mu[(size_t)pb * (m / 3) + r / 3];
+    const size_t slot = (size_t)pb * (m / 3) + r / 3;
+    const int limKind = lim ? lim[slot] : 0;
+    const double bnd = (JF && bound) ? bound[slot] : 0.0;
+    const bool pseudo = limKind != 0 || bnd > 0.0;            // a joint pseudo-contact: no friction (crMuOf of a body code)
+    double mr = pseudo ? 0.0 : mu[slot];
     if (!(mr > 1e-3)) mr = 0.0;
+    if (JF && bnd > 0.0 && (r % 3) == 0) mr = bnd;            // the bound f dt of a joint friction row (genBoxRow)
     R.mu[r] = mr; R.Bv[r] = b[(size_t)pb * m + r];
     R.fric[r] = (r % 3) != 0; R.fp[r] = r - (r % 3);
-    R.lim[r] = 0; R.neg[r] = 0; R.rowOn[r] = 1;
+    R.lim[r] = (pseudo && (r % 3) == 0) ? 1 : 0; R.neg[r] = (R.lim[r] && limKind == 2) ? 1 : 0; R.rowOn[r] = 1;
+    nLimMine += R.lim[r];
     R.on[r] = on ? on[(size_t)pb * m + r] : 1;
     double cn = 0.0;
     if (R.on[r]) for (int i = 0; i < m; i++) { const double a = Ap[(size_t)i * GR + r]; cn = fma(a, a, cn); }
     R.colNorm[r] = cn;
     R.X[r] = (haveCache && R.on[r]) ? xcache[(size_t)pb * m + r] : 0.0;
   }
+  R.anyLim = (int)w.sumAll((double)nLimMine) > 0;
   w.sync();
   bool pinvValid = false;
   GenClasses K;
   double cfmG = 0.0;
   uint32_t stG = 0x2u | 0x100u;
-  if (!genStage0(w, Ap, GR, R, S, haveCache != 0, pinvValid, K)) genCascade(w, Ap, GR, R, S, fallbackCfm, cfmG, stG, pinvValid, K);
+  if (!genStage0<GenWaveDev, JF>(w, Ap, GR, R, S, haveCache != 0, pinvValid, K)) genCascade<GenWaveDev, JF>(w, Ap, GR, R, S, fallbackCfm, cfmG, stG, pinvValid, K);
   for (int r = ln; r < m; r += 64) { x[(size_t)pb * m + r] = R.X[r]; cls[(size_t)pb * m + r] = R.on[r] ? R.cls[r] : 0; }
   if (ln == 0) { st[pb] = stG; cfmOut[pb] = cfmG; }
 }

@@ -1229,15 +1229,28 @@ int32_t nbl_selftest_lcp_dantzig_timed(int32_t count, int32_t n, const double* A
 // ---- self-test: the solver cascade of the general instantiation on caller-supplied contact LCPs (host pointers) ---------------------
 int32_t nbl_selftest_lcp_cascade(int32_t count, int32_t mRows, const double* A, const double* b, const double* mu, int32_t have_cache,
                                  const double* x_cache, const uint8_t* on, double fallback_cfm, double* x, int32_t* cls, uint32_t* st, double* cfm) {
+  return nbl_selftest_lcp_cascade_rows(count, mRows, A, b, mu, nullptr, nullptr, have_cache, x_cache, on, fallback_cfm, x, cls, st, cfm);
+}
+
+// ... with joint-limit and joint-friction slots (bound / lim per slot, NULL: none): the JF instantiation iff any bound is > 0
+int32_t nbl_selftest_lcp_cascade_rows(int32_t count, int32_t mRows, const double* A, const double* b, const double* mu, const double* bound,
+                                      const uint8_t* lim, int32_t have_cache, const double* x_cache, const uint8_t* on, double fallback_cfm,
+                                      double* x, int32_t* cls, uint32_t* st, double* cfm) {
 #if NBL_GENERAL
   if (!A || !b || !mu || !x || !cls || !st || !cfm || (have_cache && !x_cache)) return fail(NBL_E_BADARG, "null argument");
   if (count <= 0 || mRows <= 0 || mRows > MAX_ROWS || mRows % 3) return fail(NBL_E_BADARG, "count must be positive and m a multiple of 3 up to " + std::to_string(MAX_ROWS));
   if (nbl_device_count() <= 0) return fail(NBL_E_NOGPU, "no HIP device visible");
   if (const int32_t rcS = selftestScratchCheck("nbl_selftest_lcp_cascade", count)) return rcS;
   const size_t nv = (size_t)count * mRows, nm = nv * mRows, nc = (size_t)count * (mRows / 3);
-  double *dA = nullptr, *dv = nullptr, *dS = nullptr;
+  bool jf = false;
+  if (bound) for (size_t k = 0; k < nc; k++) {
+    if (!(bound[k] >= 0.0)) return fail(NBL_E_BADARG, "a bound must be >= 0");
+    if (bound[k] > 0.0) jf = true;
+  }
+  if (lim) for (size_t k = 0; k < nc; k++) if (lim[k] > 2) return fail(NBL_E_BADARG, "lim must be 0, 1 or 2");
+  double *dA = nullptr, *dv = nullptr, *dS = nullptr, *dBound = nullptr;
   int32_t* di = nullptr;
-  uint8_t* dOn = nullptr;
+  uint8_t *dOn = nullptr, *dLim = nullptr;
   hipError_t e = hipMalloc((void**)&dA, nm * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&dv, (3 * nv + nc + count) * sizeof(double));       // b, xcache, x, mu, cfm
   if (e == hipSuccess) e = hipMalloc((void**)&di, (nv + count) * sizeof(int32_t));
@@ -1248,10 +1261,19 @@ int32_t nbl_selftest_lcp_cascade(int32_t count, int32_t mRows, const double* A, 
   if (e == hipSuccess && have_cache) e = hipMemcpy(dv + nv, x_cache, nv * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dv + 3 * nv, mu, nc * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess && on) e = hipMemcpy(dOn, on, nv, hipMemcpyHostToDevice);
+  if (e == hipSuccess && jf) e = hipMalloc((void**)&dBound, nc * sizeof(double));
+  if (e == hipSuccess && jf) e = hipMemcpy(dBound, bound, nc * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && lim) e = hipMalloc((void**)&dLim, nc);
+  if (e == hipSuccess && lim) e = hipMemcpy(dLim, lim, nc, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_selftest_cascade_gen, dim3((unsigned)count), dim3(64), genRowsDoubles(GR) * sizeof(double), 0, count, mRows, dA, dv, dv + 3 * nv, have_cache, dv + nv, dOn, fallback_cfm,
-                       dv + 2 * nv, di, (uint32_t*)(di + nv), dv + 3 * nv + nc, dS);
-    e = hipDeviceSynchronize();
+    if (jf)
+      hipLaunchKernelGGL(k_selftest_cascade_gen<true>, dim3((unsigned)count), dim3(64), genRowsDoubles(GR) * sizeof(double), 0, count, mRows, dA, dv, dv + 3 * nv, dBound, dLim, have_cache,
+                         dv + nv, dOn, fallback_cfm, dv + 2 * nv, di, (uint32_t*)(di + nv), dv + 3 * nv + nc, dS);
+    else
+      hipLaunchKernelGGL(k_selftest_cascade_gen<false>, dim3((unsigned)count), dim3(64), genRowsDoubles(GR) * sizeof(double), 0, count, mRows, dA, dv, dv + 3 * nv, dBound, dLim, have_cache,
+                         dv + nv, dOn, fallback_cfm, dv + 2 * nv, di, (uint32_t*)(di + nv), dv + 3 * nv + nc, dS);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess) e = hipMemcpy(x, dv + 2 * nv, nv * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(cls, di, nv * sizeof(int32_t), hipMemcpyDeviceToHost);
@@ -1262,9 +1284,12 @@ int32_t nbl_selftest_lcp_cascade(int32_t count, int32_t mRows, const double* A, 
   if (di) hipFree(di);
   if (dS) hipFree(dS);
   if (dOn) hipFree(dOn);
+  if (dBound) hipFree(dBound);
+  if (dLim) hipFree(dLim);
   if (e != hipSuccess) return fail(NBL_E_HIP, std::string("nbl_selftest_lcp_cascade: ") + hipGetErrorString(e));
   return NBL_OK;
 #else
+  (void)bound; (void)lim;
   (void)count; (void)mRows; (void)A; (void)b; (void)mu; (void)have_cache; (void)x_cache; (void)on; (void)fallback_cfm; (void)x; (void)cls; (void)st; (void)cfm;
   return fail(NBL_E_UNSUPPORTED, "nbl_selftest_lcp_cascade addresses the general instantiation");
 #endif

@@ -173,6 +173,103 @@ def contact_lcp(rng, nc, ndof, cfm=0.0):
     return np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64), lo, hi, fi
 
 
+class BoxedLcp(tuple):
+    """What boxed_lcp returns: unpacks as (A, b, lo, hi, findex) - the problem in the DEVICE's slot layout - and carries the rest by name."""
+    def __new__(cls, **kw):
+        self = super().__new__(cls, (kw["A"], kw["b"], kw["lo"], kw["hi"], kw["findex"]))
+        self.__dict__.update(kw)
+        return self
+
+
+def boxed_lcp(rng, n_contacts, n_box, ndof, n_limit=0, dofs=None, betas=None):
+    """A boxed LCP with the three kinds of slot the general kernels carry, in the DEVICE's slot layout (three rows per slot): first the
+    contacts [normal, t1, t2] (bounds as in contact_lcp), then n_box joint-friction slots - the fixed bounds [-beta, beta] and findex -1 on
+    the first row, two EMPTY tangent rows -, then n_limit joint-limit slots - [0, inf) on the first row, two empty tangent rows; every
+    second one is of the negated kind, (-inf, 0] in the reference's problem, which the device carries as the negated row.
+    Physical: A = J M^-1 J^T with a random symmetric positive definite M (ndof x ndof), contact rows of J random, box and limit rows unit
+    vectors e_d on DISTINCT DOFs (dofs: the DOF of every box / limit slot instead - repeats allowed, for the merge tests); b random with
+    the scale mix of contact_lcp; a box row has b = -qdot_d, and beta = |b_d / A_dd| times 0.4 or 2.5 (betas: given instead), so that
+    about half of them slide (alone such a row ends on a bound) and half stick (strictly inside).  Needs n_box + n_limit <= ndof.
+
+    Returns a BoxedLcp: (A, b, lo, hi, findex) of the 3 * slots device rows (empty tangent rows: zero rows and columns of A, lo = hi = 0),
+    and by name
+      mu [slot], bound [slot] (beta, 0 on the other slots), lim [slot] (0, 1, 2 = negated): what the shims and the self-test take,
+      lim_rows, neg_rows [row] (bytes): the same per row, as gen_shim.cpp's fillRows takes them,
+      rows: the device rows that are rows of the reference's problem, in order (everything but the empty tangent rows) - and
+      A_ref, b_ref, lo_ref, hi_ref, findex_ref: that compacted problem as the reference's functions get it (what genLoadProblem builds,
+      up to the sign map),
+      S [row] = -1 on the negated limit rows, +1 elsewhere: A = S A_ref' S, b = S b_ref', x_ref' = S x (' = scattered to the device rows);
+      s_ref = S[rows]."""
+    slots = n_contacts + n_box + n_limit
+    m = 3 * slots
+    n_pseudo = n_box + n_limit
+    if dofs is None:
+        assert n_pseudo <= ndof
+        dofs = rng.choice(ndof, n_pseudo, replace=False)
+    J = np.zeros((m, ndof))
+    J[:3 * n_contacts] = rng.normal(0, 1, (3 * n_contacts, ndof))
+    for k, d in enumerate(dofs):
+        J[3 * (n_contacts + k), d] = 1.0
+    G = rng.normal(0, 1, (ndof, ndof))
+    M = G @ np.diag(rng.uniform(0.5, 5.0, ndof)) @ G.T / ndof + np.diag(rng.uniform(0.5, 2.0, ndof))
+    A = J @ np.linalg.solve(M, J.T)
+    A = 0.5 * (A + A.T)
+    b = rng.normal(0, 1, m) * rng.choice([1, 0.01])
+    mu = np.zeros(slots); bound = np.zeros(slots); lim = np.zeros(slots, np.uint8)
+    mu[:n_contacts] = rng.choice([0.5, 1.0], n_contacts)
+    for s in range(n_contacts, slots):
+        r = 3 * s
+        if s < n_contacts + n_box:
+            k = s - n_contacts
+            bound[s] = betas[k] if betas is not None else abs(b[r] / A[r, r]) * rng.choice([0.4, 2.5])
+        else:
+            lim[s] = 2 if (s - n_contacts - n_box) % 2 else 1
+    return slots_lcp(A, b, mu, bound, lim)
+
+
+def slots_lcp(A, b, mu, bound, lim):
+    """The BoxedLcp (boxed_lcp) of 3 * slots device rows A, b and the per-slot description mu / bound / lim: bounds, findex, the rows of
+    the reference's problem and that problem.  A slot with bound > 0 is a joint-friction slot, one with lim > 0 a joint-limit slot, every
+    other one a contact (mu <= 1e-3: frictionless, its tangent rows empty like a pseudo-contact's)."""
+    mu = np.where(np.asarray(mu, float) > 1e-3, mu, 0.0); bound = np.asarray(bound, float); lim = np.asarray(lim, np.uint8)
+    slots = len(mu); m = 3 * slots
+    A = np.array(A, dtype=np.float64); b = np.array(b, dtype=np.float64)
+    pseudo = (bound > 0) | (lim > 0)
+    mu = np.where(pseudo, 0.0, mu)
+    lo = np.zeros(m); hi = np.zeros(m); fi = np.full(m, -1, np.int32)
+    S = np.ones(m)
+    keep = np.zeros(m, bool)
+    for s in range(slots):
+        r = 3 * s
+        fi[r + 1] = fi[r + 2] = r
+        keep[r] = True
+        if mu[s] > 0:
+            keep[r + 1] = keep[r + 2] = True
+            lo[r + 1] = lo[r + 2] = -mu[s]; hi[r + 1] = hi[r + 2] = mu[s]
+        else:                                          # empty tangent rows: not rows of the problem
+            A[r + 1:r + 3, :] = 0.0; A[:, r + 1:r + 3] = 0.0; b[r + 1:r + 3] = 0.0
+        if bound[s] > 0:
+            lo[r] = -bound[s]; hi[r] = bound[s]
+        else:
+            hi[r] = np.inf
+            if lim[s] == 2:
+                S[r] = -1.0
+    rows = np.where(keep)[0]
+    lim_rows = np.zeros(m, np.uint8); neg_rows = np.zeros(m, np.uint8)
+    lim_rows[0::3] = pseudo; neg_rows[0::3] = lim == 2
+    # the reference's problem: the compacted rows, the negated limit rows in the reference's own sign ((-inf, 0])
+    sr = S[rows]
+    A_ref = np.ascontiguousarray(sr[:, None] * A[np.ix_(rows, rows)] * sr[None, :])
+    b_ref = sr * b[rows]
+    lo_ref = np.where(sr < 0, -hi[rows], lo[rows]) + 0.0
+    hi_ref = np.where(sr < 0, -lo[rows], hi[rows]) + 0.0
+    pos = {int(r): i for i, r in enumerate(rows)}
+    fi_ref = np.array([-1 if fi[r] < 0 else pos[int(fi[r])] for r in rows], dtype=np.int32)
+    return BoxedLcp(A=np.ascontiguousarray(A), b=np.ascontiguousarray(b), lo=lo, hi=hi, findex=fi, mu=np.ascontiguousarray(mu), bound=np.ascontiguousarray(bound),
+                    lim=np.ascontiguousarray(lim), lim_rows=lim_rows, neg_rows=neg_rows, rows=rows, S=S, s_ref=sr, A_ref=A_ref, b_ref=np.ascontiguousarray(b_ref),
+                    lo_ref=np.ascontiguousarray(lo_ref), hi_ref=np.ascontiguousarray(hi_ref), findex_ref=fi_ref)
+
+
 def have_ref():
     """oracle/_ref (the reference's own Dantzig solver compiled from its vendored sources) is present."""
     import os
