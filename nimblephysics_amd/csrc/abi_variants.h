@@ -6,9 +6,14 @@
  *   NBL_MAXC = 128 the same general code with 384 rows (suffix _c128, device namespace nbl_c128): only for models that ask for more than 64
  *                  contact slots (its per-world scratch and record are four times the 192-row build's)
  * Each instantiation is one translation unit (nimble_amd.hip compiled with -DNBL_MAXC=.. -DNBL_VARIANT_SUFFIX=..); this header,
- * included before include/nimble_amd.h, renames the ABI's entry points and its opaque handle type with the suffix so that both fit in
- * one shared library.  nimble_amd_dispatch.cpp exports the names of include/nimble_amd.h and hands every model to the instantiation
- * that fits it (nbl_model_create).  Without NBL_VARIANT_SUFFIX nothing is renamed: nimble_amd.hip alone is then the whole library
+ * included before include/nimble_amd.h, renames the entry points that exist PER CAPACITY, and the opaque handle type, with the suffix so
+ * that all fit in one shared library: model creation, the step, the rollouts, inertia patches, slices, timing, the self-tests and the
+ * contact read-out - whatever reads LCP rows, collider budgets or the saved record.  nimble_amd_dispatch.cpp exports those names of
+ * include/nimble_amd.h and hands every model to the instantiation that fits it (nbl_model_create).
+ * The CONTACT-INDEPENDENT calls - kinematics maps, inverse and forward dynamics, mass matrix, wrenches, inertia-parameter gradients, IK,
+ * body sets and centroidal quantities, sensors - are not renamed and not dispatched: nimble_amd_tree.hip defines them once, under their
+ * public names, over the capacity-independent base of a handle (tree_model_host.hpp; nbl_model_tree below hands it out).
+ * Without NBL_VARIANT_SUFFIX nothing is renamed: nimble_amd.hip alone, which then includes nimble_amd_tree.hip, is the whole library
  * in its 8-contact form (the developer builds of tools/ compile it that way).
  */
 #ifndef NBL_ABI_VARIANTS_H
@@ -71,46 +76,10 @@
 #define nbl_version NBL_V(nbl_version)
 #define nbl_workspace_bytes NBL_V(nbl_workspace_bytes)
 #define nbl_model_max_contacts NBL_V(nbl_model_max_contacts)
-#define nbl_kin_map NBL_V(nbl_kin_map)
-#define nbl_kin_map_create NBL_V(nbl_kin_map_create)
-#define nbl_kin_map_destroy NBL_V(nbl_kin_map_destroy)
-#define nbl_kin_map_dim NBL_V(nbl_kin_map_dim)
-#define nbl_kinematics_forward NBL_V(nbl_kinematics_forward)
-#define nbl_kinematics_backward NBL_V(nbl_kinematics_backward)
-#define nbl_dynamics_workspace_bytes NBL_V(nbl_dynamics_workspace_bytes)
-#define nbl_inverse_dynamics_forward NBL_V(nbl_inverse_dynamics_forward)
-#define nbl_inverse_dynamics_backward NBL_V(nbl_inverse_dynamics_backward)
-#define nbl_mass_matrix NBL_V(nbl_mass_matrix)
-#define nbl_forward_dynamics_workspace_bytes NBL_V(nbl_forward_dynamics_workspace_bytes)
-#define nbl_forward_dynamics_forward NBL_V(nbl_forward_dynamics_forward)
-#define nbl_forward_dynamics_backward NBL_V(nbl_forward_dynamics_backward)
-#define nbl_inv_mass_apply NBL_V(nbl_inv_mass_apply)
-#define nbl_inv_mass_matrix NBL_V(nbl_inv_mass_matrix)
-#define nbl_ik_default_config NBL_V(nbl_ik_default_config)
-#define nbl_ik_workspace_bytes NBL_V(nbl_ik_workspace_bytes)
-#define nbl_ik_solve NBL_V(nbl_ik_solve)
-#define nbl_wrench_workspace_bytes NBL_V(nbl_wrench_workspace_bytes)
-#define nbl_inverse_dynamics_wrench_forward NBL_V(nbl_inverse_dynamics_wrench_forward)
-#define nbl_inverse_dynamics_wrench_backward NBL_V(nbl_inverse_dynamics_wrench_backward)
-#define nbl_forward_dynamics_wrench_forward NBL_V(nbl_forward_dynamics_wrench_forward)
-#define nbl_forward_dynamics_wrench_backward NBL_V(nbl_forward_dynamics_wrench_backward)
-#define nbl_contact_inverse_dynamics NBL_V(nbl_contact_inverse_dynamics)
-#define nbl_inverse_dynamics_backward_inertia NBL_V(nbl_inverse_dynamics_backward_inertia)
-#define nbl_forward_dynamics_backward_inertia NBL_V(nbl_forward_dynamics_backward_inertia)
 #define nbl_contact_readout NBL_V(nbl_contact_readout)
 #define nbl_contact_readout_rows NBL_V(nbl_contact_readout_rows)
 #define nbl_contact_body_wrenches NBL_V(nbl_contact_body_wrenches)
-#define nbl_body_set NBL_V(nbl_body_set)
-#define nbl_body_set_create NBL_V(nbl_body_set_create)
-#define nbl_body_set_destroy NBL_V(nbl_body_set_destroy)
-#define nbl_body_set_mass NBL_V(nbl_body_set_mass)
-#define nbl_body_set_origin_moments NBL_V(nbl_body_set_origin_moments)
-#define nbl_centroidal_workspace_bytes NBL_V(nbl_centroidal_workspace_bytes)
-#define nbl_centroidal_forward NBL_V(nbl_centroidal_forward)
-#define nbl_centroidal_backward NBL_V(nbl_centroidal_backward)
-#define nbl_sensors_workspace_bytes NBL_V(nbl_sensors_workspace_bytes)
-#define nbl_sensors_forward NBL_V(nbl_sensors_forward)
-#define nbl_sensors_backward NBL_V(nbl_sensors_backward)
+#define nbl_model_tree NBL_V(nbl_model_tree)   /* (not in the ABI: the handle's base for nimble_amd_tree.hip, tree_model_host.hpp) */
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

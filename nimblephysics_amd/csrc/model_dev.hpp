@@ -43,25 +43,10 @@
 #define NBL_W_BFINAL 1
 #endif
 
-// The device namespace of this instantiation of the library (the library is built several times from one set of sources, see
-// abi_variants.h: every build names its own - -DNBL_NS=nbl_c16 - so that their kernels and constants never meet at link time).
-#ifndef NBL_NS
-#define NBL_NS nbl
-#endif
-namespace NBL_NS {
-
-// Developer instrumentation (tools/phase_timing.py builds with -DNBL_PHASE_TIMING): cycle stamps of the first wavefront of a
-// launch at phase boundaries of the tree kernels.  Compiled out of the shipped library.
-#ifdef NBL_PHASE_TIMING
-__device__ unsigned long long g_phaseStamp[64];
-#define NBL_PHASE(k) do { if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) g_phaseStamp[k] = clock64(); } while (0)
-#define NBL_PHASE_FIRST(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phaseStamp[k] = clock64(); } while (0)   // (the narrow-phase workgroups come first)
-#else
-#define NBL_PHASE(k) do { } while (0)
-#define NBL_PHASE_FIRST(k) do { } while (0)
-#endif
-
-constexpr int JT_REVOLUTE = 0, JT_PRISMATIC = 1, JT_FREE = 2, JT_BALL = 4, JT_SCREW = 5, JT_FREEC = 6;   // = NBL_JOINT_*; JT_BALL: one of the three coincident axes of a ball joint; JT_FREEC (internal): one of the SIX coincident axes (3 rotations, 3 translations) of a free joint below the root
+// The tree model's constants.  ONE type in every build: the instantiations of the contact stage and the unit of the contact-independent
+// calls (nimble_amd_tree.hip, built once) share a model handle's host-side base (tree_model_host.hpp), so these live in a fixed namespace
+// and every device namespace pulls them in by name (below).
+namespace nbl_shared {
 
 struct DevBody {
   int32_t parent, jtype, dofOff, ndof;
@@ -101,6 +86,33 @@ struct DevModel {
   double dt;
   int64_t b0, b1;     // the worlds [b0, b1) this launch processes (the batch may be sliced over several HIP streams)
 };
+
+}  // namespace nbl_shared
+
+// The device namespace of this instantiation of the library (the library is built several times from one set of sources, see
+// abi_variants.h: every build names its own - -DNBL_NS=nbl_c16 - so that their kernels and constants never meet at link time).
+#ifndef NBL_NS
+#define NBL_NS nbl
+#endif
+namespace NBL_NS {
+
+using nbl_shared::DevBody;
+using nbl_shared::DevDof;
+using nbl_shared::DevInertiaParam;
+using nbl_shared::DevModel;
+
+// Developer instrumentation (tools/phase_timing.py builds with -DNBL_PHASE_TIMING): cycle stamps of the first wavefront of a
+// launch at phase boundaries of the tree kernels.  Compiled out of the shipped library.
+#ifdef NBL_PHASE_TIMING
+__device__ unsigned long long g_phaseStamp[64];
+#define NBL_PHASE(k) do { if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) g_phaseStamp[k] = clock64(); } while (0)
+#define NBL_PHASE_FIRST(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phaseStamp[k] = clock64(); } while (0)   // (the narrow-phase workgroups come first)
+#else
+#define NBL_PHASE(k) do { } while (0)
+#define NBL_PHASE_FIRST(k) do { } while (0)
+#endif
+
+constexpr int JT_REVOLUTE = 0, JT_PRISMATIC = 1, JT_FREE = 2, JT_BALL = 4, JT_SCREW = 5, JT_FREEC = 6;   // = NBL_JOINT_*; JT_BALL: one of the three coincident axes of a ball joint; JT_FREEC (internal): one of the SIX coincident axes (3 rotations, 3 translations) of a free joint below the root
 
 // Workspace slots per body (doubles per world).
 constexpr int WS_T = 0;        // 12  relative transform T = T_pj Q(q) T_cj^-1

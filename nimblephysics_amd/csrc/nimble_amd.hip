@@ -13,8 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "abi_variants.h"   // (before the ABI header: the two instantiations of the library rename its entry points, see there)
+#include "abi_variants.h"   // (before the ABI header: the instantiations of the library rename its entry points, see there)
 #include "../../include/nimble_amd.h"
+#include "tree_model_host.hpp"
 #include "kernels.hip"
 #include "contact_kernels.hip"
 #include "contact_backward.hip"
@@ -25,11 +26,6 @@
 #endif
 #include "coop_tree.hip"
 #include "inertia_backward.hip"
-#include "kinematics.hip"
-#include "dynamics.hip"
-#include "centroidal.hip"
-#include "sensors.hip"
-#include "ik.hip"
 #include "contact_readout.hip"
 
 using namespace NBL_NS;
@@ -40,37 +36,16 @@ int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) return fail(NBL_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 constexpr int NBL_MAX_SLICES = 8;
-enum KernelId { K_FWD = 0, K_DETECT, K_BWD, K_RECOMPUTE, K_BWD_FINAL, K_SOLVE_COOP, K_BWD_A_COOP, K_ROWS_COOP, K_BWD_B_COOP, K_FWD_COOP, K_RECOMPUTE_COOP, K_BWD_FINAL_COOP, K_TREE_TO_LANES, K_CASCADE_COOP, K_CASCADE_FINAL, K_BWD_BOUNCE, K_CASCADE_FUSED, K_FWD_DETECT, K_CENTROIDAL, K_CENTROIDAL_VJP, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"k_step_forward", "k_contact_detect",
-                                           "k_step_backward", "k_bwd_recompute",
-                                           "k_bwd_final", "k_contact_solve_coop", "k_bwd_contact_a_coop", "k_contact_rows_coop", "k_bwd_contact_b_coop", "k_step_forward_coop", "k_bwd_recompute_coop",
-                                           "k_bwd_final_coop", "k_tree_to_lanes", "k_contact_cascade_stages", "k_contact_cascade_final", "k_bwd_bounce", "k_contact_cascade_fused", "k_forward_detect_coop",
-                                           "k_centroidal", "k_centroidal_vjp"};
-struct TimedLaunch {
-  hipEvent_t start, stop;
-  int kernel;
-};
 }  // namespace
 
-struct nbl_model {
-  int device = 0;
-  DevModel mdl;
-  DevBody* dBodies = nullptr;
-  DevDof* dDofs = nullptr;
-  int nb = 0, n = 0, k = 0, maxContacts = 0;
+// (the base holds what the contact-independent calls read: tree_model_host.hpp)
+struct nbl_model : nbl_tree_model {
+  int k = 0, maxContacts = 0;
   bool hasContact = false;
   DevContactModel* dContact = nullptr;
   SavedLayout lay;
-  bool timing = false;      // kernel timing requested
-  bool timingNow = false;   // ... and this call is one of the sampled ones
-  int timingPeriod = 1;     // every timingPeriod-th forward / backward call carries HIP events
+  int timingPeriod = 1;    // every timingPeriod-th forward / backward call carries HIP events
   int64_t fwdCalls = 0, bwdCalls = 0;
   int slices = 0;                    // batch slices over HIP streams (0 = auto), nbl_set_slices / NBL_SLICES
   bool deferJoin = false;            // nbl_set_deferred_join: every slice on an internal stream, calls return without joining (nbl_join_slices joins)
@@ -102,20 +77,11 @@ struct nbl_model {
   bool coopFinal = true;             // the backward sweeps too, in the world frame (NBL_COOP_FINAL=0: one world per lane, fed by k_tree_to_lanes)
   bool coopTree = false;             // tree sweeps one world per wavefront (needs the saved tree block, nb and n <= 64)
   int treeLanes = 0;                 // worlds per workgroup of the one-world-per-lane tree kernels (0 = pick from B); nbl_set_launch_lanes
-  std::vector<DevBody> hBodies;      // host copy of the body constants (nbl_set_body_inertia patches one entry)
-  int userBodies = 0;                // bodies of the caller's description; bodyMap: caller's body index -> device body (empty: identity;
-  std::vector<int32_t> bodyMap;      // models with ball joints carry two extra massless bodies per ball joint, expandBallJoints)
-  int deviceBody(int body) const { return bodyMap.empty() ? body : bodyMap[body]; }
-  DevInertiaParam* dParams = nullptr; // registered inertia parameters (nbl_set_inertia_params)
-  int nParams = 0;
   void* staging = nullptr;           // pinned host staging area of the stream-ordered uploads (nbl_set_body_inertias)
   size_t stagingBytes = 0;
   hipEvent_t staged = nullptr;       // recorded after the last upload that reads the staging area
-  std::vector<TimedLaunch> pending;
   double fwdMs = 0, bwdMs = 0;
   int64_t fwdCount = 0, bwdCount = 0;
-  double kMs[K_COUNT] = {0};
-  int64_t kCount[K_COUNT] = {0};
 };
 
 // spatial inertia (Inertia.cpp:1368-1383), packed symmetric (upper triangle, row by row)
@@ -557,6 +523,7 @@ int32_t nbl_model_create(const nbl_model_desc* d, int32_t device, nbl_model** ou
   }
 
   nbl_model* m = new nbl_model();
+  m->capacity = MAX_CONTACTS;
   m->hasContact = hasContact;
   m->multiGroup = multiGroupModel;
   m->jointFriction = !fricDofs.empty();
@@ -758,23 +725,6 @@ static int pickLanes(int64_t B, int requested, int maxLanes) {
   if (l < 1) l = 1;
   return l;
 }
-static void beginTiming(nbl_model* m, hipStream_t s, int kernel) {
-  if (!m->timingNow) return;
-  TimedLaunch t;
-  hipEventCreate(&t.start);
-  hipEventCreate(&t.stop);
-  t.kernel = kernel;
-  hipEventRecord(t.start, s);
-  m->pending.push_back(t);
-}
-static void endTiming(nbl_model* m, hipStream_t s) {
-  if (!m->timingNow) return;
-  hipEventRecord(m->pending.back().stop, s);
-}
-// NBL_DEBUG_SYNC=1 (developer switch): wait for every kernel and name it on stderr - a device fault then points at its launch
-static const bool g_dbgSync = getenv("NBL_DEBUG_SYNC") && atoi(getenv("NBL_DEBUG_SYNC")) != 0;
-#define TIMED(kid, launch) do { beginTiming(m, s, kid); launch; endTiming(m, s); \
-    if (g_dbgSync) { const hipError_t de_ = hipStreamSynchronize(s); fprintf(stderr, "[nbl] %s: %s\n", kKernelNames[kid], hipGetErrorString(de_)); } } while (0)
 
 // the kernels of one forward step for the worlds [b0, b1) on stream s (slice si owns fail list / counter si)
 static int32_t launchForward(nbl_model* m, int64_t B, int si, int64_t b0, int64_t b1, hipStream_t s, const double* state,
@@ -1021,13 +971,6 @@ int32_t nbl_step_backward(nbl_model* m, int64_t B, const void* saved, const doub
 // ---- inertia ("mass") parameters: World::setMasses / lossWrtMass (World.cpp:1821-1824, BackpropSnapshot.cpp:167-179) ----
 extern "C++" {   // (internal helpers: C++ linkage keeps them local to this instantiation of the library)
 namespace {
-// keeps the calling thread's current device across an entry point that has to work on the model's device
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 // pinned staging area of a model (stream-ordered uploads read from it; `staged` marks the last upload still reading it)
 int32_t ensureStaging(nbl_model* m, size_t bytes) {
   if (m->stagingBytes >= bytes) return NBL_OK;
@@ -1727,483 +1670,6 @@ int32_t nbl_kernel_timing(nbl_model* m, int32_t i, double* ms_sum, int64_t* coun
   return NBL_OK;
 }
 
-// ---- world-space kinematics of body frames (IKMapping, map_to_pos / map_to_vel; csrc/kinematics.hip) ----------------------------------
-struct nbl_kin_map {
-  int device = 0;
-  int count = 0, P = 0, n = 0, nb = 0;   // entries, mapped rows, DOFs and device bodies of the model it was made for
-  void* dBuf = nullptr;                  // [count] DevKinEntry, then the ancestor chains (int32 device bodies, root -> entry body)
-  DevKinEntry* dEntries = nullptr;
-  int32_t* dPath = nullptr;
-  std::vector<DevKinEntry> hEntries;     // host copies: what the wrench calls check before they launch
-  std::vector<int32_t> hPath;
-};
-
-int32_t nbl_kin_map_create(nbl_model* m, int32_t count, const int32_t* kind, const int32_t* body, const double* T_offset, nbl_kin_map** out) {
-  if (!m || !out || !kind || !body) return fail(NBL_E_BADARG, "null argument");
-  *out = nullptr;
-  if (count < 1) return fail(NBL_E_BADARG, "a kinematics map needs at least one entry");
-  if (count > KIN_MAX_ENTRIES)
-    return fail(NBL_E_BADARG, "a kinematics map holds at most " + std::to_string(KIN_MAX_ENTRIES) + " entries (" +
-                                  std::to_string(6 * KIN_MAX_ENTRIES) + " rows); got " + std::to_string(count));
-  std::vector<DevKinEntry> he(count);
-  std::vector<int32_t> path;
-  int row = 0;
-  for (int k = 0; k < count; k++) {
-    if (kind[k] != NBL_KIN_SPATIAL && kind[k] != NBL_KIN_LINEAR && kind[k] != NBL_KIN_ANGULAR)
-      return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": kind must be NBL_KIN_SPATIAL, NBL_KIN_LINEAR or NBL_KIN_ANGULAR");
-    if (body[k] < -1 || body[k] >= m->userBodies)
-      return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": body " + std::to_string(body[k]) + " out of range [-1, " + std::to_string(m->userBodies) + ")");
-    DevKinEntry& e = he[k];
-    std::memset(&e, 0, sizeof(e));
-    e.kind = kind[k];
-    e.row = row;
-    row += kinRows(kind[k]);
-    static const double I12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    for (int c = 0; c < 12; c++) e.T[c] = T_offset ? T_offset[12 * k + c] : I12[c];
-    for (int c = 0; c < 12; c++)
-      if (!std::isfinite(e.T[c])) return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": non-finite offset transform");
-    // the ancestor chain of the device body that carries T_cj (the z body of a ball triple, the last body of a free chain), root first
-    std::vector<int32_t> chain;
-    for (int i = body[k] < 0 ? -1 : m->deviceBody(body[k]); i >= 0; i = m->hBodies[i].parent) chain.push_back(i);
-    e.pathBegin = (int32_t)path.size();
-    e.pathLen = (int32_t)chain.size();
-    path.insert(path.end(), chain.rbegin(), chain.rend());
-  }
-  nbl_kin_map* km = new nbl_kin_map();
-  km->device = m->device; km->count = count; km->P = row; km->n = m->n; km->nb = m->nb;
-  const size_t eb = sizeof(DevKinEntry) * count, bytes = eb + sizeof(int32_t) * std::max<size_t>(path.size(), 1);
-  std::vector<char> img(bytes, 0);
-  std::memcpy(img.data(), he.data(), eb);
-  if (!path.empty()) std::memcpy(img.data() + eb, path.data(), sizeof(int32_t) * path.size());
-  {
-    DeviceGuard guard(m->device);
-    hipError_t e = guard.ok ? hipMalloc(&km->dBuf, bytes) : hipErrorInvalidDevice;
-    if (e == hipSuccess) e = hipMemcpy(km->dBuf, img.data(), bytes, hipMemcpyHostToDevice);   // (registration time: synchronous)
-    if (e != hipSuccess) {
-      const std::string msg = std::string("kinematics map upload: ") + hipGetErrorString(e);
-      if (km->dBuf) (void)hipFree(km->dBuf);
-      delete km;
-      return fail(NBL_E_HIP, msg);
-    }
-  }
-  km->dEntries = (DevKinEntry*)km->dBuf;
-  km->dPath = (int32_t*)((char*)km->dBuf + eb);
-  km->hEntries = he;
-  km->hPath = path;
-  *out = km;
-  return NBL_OK;
-}
-
-void nbl_kin_map_destroy(nbl_kin_map* k) {
-  if (!k) return;
-  if (k->dBuf) {
-    DeviceGuard guard(k->device);
-    (void)hipFree(k->dBuf);   // (waits for launches that still read it)
-  }
-  delete k;
-}
-
-int32_t nbl_kin_map_dim(const nbl_kin_map* k) { return k ? k->P : 0; }
-
-static int32_t kinCheck(const nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state) {
-  if (!m || !k || !state) return fail(NBL_E_BADARG, "null argument");
-  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  if (B <= 0) return fail(NBL_E_BADARG, "B must be positive");
-  if ((B + KIN_BLOCK - 1) / KIN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  return NBL_OK;
-}
-
-int32_t nbl_kinematics_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, double* pos, double* vel, void* stream) {
-  const int32_t rc = kinCheck(m, k, B, state);
-  if (rc != NBL_OK) return rc;
-  if (!pos && !vel) return NBL_OK;
-  hipLaunchKernelGGL(k_kinematics_fwd, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, pos, vel);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_kinematics_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* grad_pos,
-                                const double* grad_vel, double* grad_state, int32_t accumulate, void* stream) {
-  const int32_t rc = kinCheck(m, k, B, state);
-  if (rc != NBL_OK) return rc;
-  if (!grad_state) return fail(NBL_E_BADARG, "null argument");
-  hipLaunchKernelGGL(k_kinematics_vjp, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, grad_pos,
-                     grad_vel, grad_state, accumulate ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-// ---- joint-space dynamics quantities (inverse dynamics, Coriolis and gravity, mass matrix; csrc/dynamics.hip) --------------------------
-size_t nbl_dynamics_workspace_bytes(const nbl_model* m, int64_t B) {
-  if (!m || B <= 0) return 0;
-  return sizeof(double) * (size_t)m->nb * DYN_SLOTS * (size_t)B;
-}
-
-static int32_t dynCheck(const nbl_model* m, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (B == 0) return NBL_OK;
-  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
-  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = nbl_dynamics_workspace_bytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "dynamics workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_dynamics_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
-}
-static int32_t dynFlags(int32_t flags) {
-  if (flags & ~DYN_FLAG_MASK) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~DYN_FLAG_MASK) + " (NBL_ID_*)");
-  return NBL_OK;
-}
-
-int32_t nbl_inverse_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags, double* tau,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  int32_t rc = dynCheck(m, B, state, tau, workspace, workspace_bytes);
-  if (rc == NBL_OK) rc = dynFlags(flags);
-  if (rc != NBL_OK || B == 0) return rc;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, tau, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_inverse_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
-                                      const double* grad_tau, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  int32_t rc = dynCheck(m, B, state, grad_tau, workspace, workspace_bytes);
-  if (rc == NBL_OK) rc = dynFlags(flags);
-  if (rc != NBL_OK || B == 0) return rc;
-  if (!grad_state && !grad_accel) return NBL_OK;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, grad_tau, grad_state, grad_accel,
-                     accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_mass_matrix(nbl_model* m, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = dynCheck(m, B, state, M, workspace, workspace_bytes);
-  if (rc != NBL_OK || B == 0) return rc;
-  DeviceGuard guard(m->device);
-  HIP_TRY(hipMemsetAsync(M, 0, sizeof(double) * (size_t)m->n * m->n * (size_t)B, (hipStream_t)stream));   // unrelated DOFs: the kernel writes the rest
-  hipLaunchKernelGGL(k_mass_matrix, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, B, state, M, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-// ---- forward dynamics and the inverse mass matrix (articulated-body algorithm; csrc/dynamics.hip) ---------------------------------------
-// workspace: [nb][FD_SLOTS][B] tree slots (the reverse pass's k_inverse_dynamics_vjp reuses them: DYN_SLOTS <= FD_SLOTS), then the
-// recomputed acceleration [n][B] and -lambda [n][B] of nbl_forward_dynamics_backward
-static_assert(DYN_SLOTS <= FD_SLOTS, "the reverse pass runs k_inverse_dynamics_vjp on the forward-dynamics tree slots");
-size_t nbl_forward_dynamics_workspace_bytes(const nbl_model* m, int64_t B) {
-  if (!m || B <= 0) return 0;
-  return sizeof(double) * ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
-}
-
-static int32_t fdynCheck(const nbl_model* m, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (B == 0) return NBL_OK;
-  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
-  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = nbl_forward_dynamics_workspace_bytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "forward-dynamics workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_forward_dynamics_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
-}
-
-int32_t nbl_forward_dynamics_forward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, double* accel,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  int32_t rc = fdynCheck(m, B, state, accel, workspace, workspace_bytes);
-  if (rc == NBL_OK) rc = dynFlags(flags);
-  if (rc != NBL_OK || B == 0) return rc;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_forward_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, accel, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_forward_dynamics_backward(nbl_model* m, int64_t B, const double* state, const double* tau, int32_t flags, const double* grad_accel,
-                                      double* grad_state, double* grad_tau, int32_t accumulate, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
-  int32_t rc = fdynCheck(m, B, state, grad_accel, workspace, workspace_bytes);
-  if (rc == NBL_OK) rc = dynFlags(flags);
-  if (rc != NBL_OK || B == 0) return rc;
-  if (!grad_state && !grad_tau) return NBL_OK;
-  DeviceGuard guard(m->device);
-  double* ws = (double*)workspace;
-  double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
-  double* neglam = accel + (size_t)m->n * (size_t)B;
-  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
-  hipLaunchKernelGGL(k_forward_dynamics_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
-                     m->mdl, (int)flags, B, state, tau, grad_accel, accel, neglam, grad_tau, accumulate ? 1 : 0, ws);
-  HIP_TRY(hipGetLastError());
-  if (grad_state) {   // grad_state (+)= -(d ID / d [q; v])^T lambda at (q, v, a): inverse dynamics is the exact inverse function
-    hipLaunchKernelGGL(k_inverse_dynamics_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
-                       m->mdl, (int)flags, B, state, (const double*)accel, (const double*)neglam, grad_state, (double*)nullptr, accumulate ? 1 : 0, ws);
-    HIP_TRY(hipGetLastError());
-  }
-  return NBL_OK;
-}
-
-int32_t nbl_inv_mass_apply(nbl_model* m, int64_t B, int32_t R, const double* state, const double* X, double* Y, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  const int32_t rc = fdynCheck(m, B, state, Y, workspace, workspace_bytes);
-  if (rc != NBL_OK) return rc;
-  if (R < 1) return fail(NBL_E_BADARG, "R must be at least 1 (got " + std::to_string(R) + ")");
-  if (B == 0) return NBL_OK;
-  if (!X && R != m->n) return fail(NBL_E_BADARG, "X may be null (the identity) only with R = n");
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, B, (int)R, state, X, Y, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_inv_mass_matrix(nbl_model* m, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = fdynCheck(m, B, state, Minv, workspace, workspace_bytes);
-  if (rc != NBL_OK || B == 0) return rc;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, B, (int)m->n, state, (const double*)nullptr, Minv, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-// ---- wrenches on body frames in the dynamics calls, contact inverse dynamics (csrc/dynamics.hip) -----------------------------------------
-// workspace: the forward-dynamics layout ([nb][FD_SLOTS][B] tree slots, accel [n][B], -lambda [n][B]), then the moments of world-frame
-// wrenches [nb][3][B] and the root-to-entry transforms of the contact solve [E][12][B]
-static size_t wrenchCount(const nbl_kin_map* k) { return k ? (size_t)k->count : 0; }
-size_t nbl_wrench_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) {
-  if (!m || B <= 0) return 0;
-  return sizeof(double) * ((size_t)m->nb * (FD_SLOTS + 3) + 2 * (size_t)m->n + 12 * wrenchCount(k)) * (size_t)B;
-}
-
-// the checks the wrench calls share; k NULL: a set with no entries
-static int32_t wrenchCheck(const nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const void* out, const double* wrench,
-                           int32_t flags, int32_t flagMask, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (k && (k->n != m->n || k->nb != m->nb || k->device != m->device)) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  if (k)
-    for (int e = 0; e < k->count; e++)
-      if (k->hEntries[e].kind != KIN_SPATIAL)
-        return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the wrench set is not NBL_KIN_SPATIAL: a wrench needs a whole frame");
-  if (flags & ~flagMask) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~flagMask) + " (NBL_ID_*, NBL_WRENCH_WORLD)");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (B == 0) return NBL_OK;
-  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
-  if (k && !wrench) return fail(NBL_E_BADARG, "null wrench array for a set of " + std::to_string(k->count) + " entries");
-  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = nbl_wrench_workspace_bytes(m, k, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "wrench workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_wrench_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
-}
-#define NBL_WRENCH_SET(k) (const DevKinEntry*)((k) ? (k)->dEntries : nullptr), (const int32_t*)((k) ? (k)->dPath : nullptr), (int)wrenchCount(k)
-
-int32_t nbl_inverse_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
-                                            const double* wrench, int32_t flags, double* tau, void* workspace, size_t workspace_bytes,
-                                            void* stream) {
-  const int32_t rc = wrenchCheck(m, k, B, state, tau, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
-  if (rc != NBL_OK || B == 0) return rc;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics_wrench, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, NBL_WRENCH_SET(k), wrench, tau,
-                     (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_inverse_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
-                                             const double* wrench, int32_t flags, const double* grad_tau, double* grad_state, double* grad_accel,
-                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = wrenchCheck(m, k, B, state, grad_tau, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
-  if (rc != NBL_OK || B == 0) return rc;
-  if (!grad_state && !grad_accel && !grad_wrench) return NBL_OK;
-  DeviceGuard guard(m->device);
-  double* ws = (double*)workspace;
-  double* wx = ws + ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
-  hipLaunchKernelGGL(k_inverse_dynamics_wrench_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, NBL_WRENCH_SET(k), wrench, grad_tau,
-                     grad_state, grad_accel, grad_wrench, accumulate ? 1 : 0, ws, wx);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_forward_dynamics_wrench_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
-                                            const double* wrench, int32_t flags, double* accel, void* workspace, size_t workspace_bytes,
-                                            void* stream) {
-  const int32_t rc = wrenchCheck(m, k, B, state, accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
-  if (rc != NBL_OK || B == 0) return rc;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_forward_dynamics_wrench, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, accel,
-                     (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_forward_dynamics_wrench_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
-                                             const double* wrench, int32_t flags, const double* grad_accel, double* grad_state, double* grad_tau,
-                                             double* grad_wrench, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = wrenchCheck(m, k, B, state, grad_accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
-  if (rc != NBL_OK || B == 0) return rc;
-  if (!grad_state && !grad_tau && !grad_wrench) return NBL_OK;
-  DeviceGuard guard(m->device);
-  double* ws = (double*)workspace;
-  double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
-  double* neglam = accel + (size_t)m->n * (size_t)B;
-  double* wx = neglam + (size_t)m->n * (size_t)B;
-  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
-  hipLaunchKernelGGL(k_forward_dynamics_wrench_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
-                     (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, grad_accel, accel, neglam, grad_tau,
-                     accumulate ? 1 : 0, ws);
-  HIP_TRY(hipGetLastError());
-  if (grad_state || grad_wrench) {   // grad_state (+)= -(d ID / d [q; v])^T lambda, grad_wrench (+)= J lambda, at (q, v, a) with the same wrenches
-    hipLaunchKernelGGL(k_inverse_dynamics_wrench_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
-                       (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, (const double*)accel, NBL_WRENCH_SET(k), wrench, (const double*)neglam,
-                       grad_state, (double*)nullptr, grad_wrench, accumulate ? 1 : 0, ws, wx);
-    HIP_TRY(hipGetLastError());
-  }
-  return NBL_OK;
-}
-
-// ---- gradients of the dynamics calls to the registered inertia parameters (k_inverse_dynamics_inertia_vjp; csrc/dynamics.hip) ------------
-// The table is the one nbl_set_inertia_params[_on] uploaded; none registered: nothing to write, success.
-int32_t nbl_inverse_dynamics_backward_inertia(nbl_model* m, int64_t B, const double* state, const double* accel, int32_t flags,
-                                              const double* grad_tau, double* grad_params, int32_t accumulate, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-  int32_t rc = dynCheck(m, B, state, grad_tau, workspace, workspace_bytes);
-  if (rc == NBL_OK) rc = dynFlags(flags);
-  if (rc != NBL_OK || B == 0 || m->nParams == 0) return rc;
-  if (!grad_params) return fail(NBL_E_BADARG, "null grad_params for " + std::to_string(m->nParams) + " registered inertia parameters");
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics_inertia_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, (int)flags, B, state, accel, grad_tau, (const DevInertiaParam*)m->dParams, m->nParams,
-                     grad_params, accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-// Two launches like nbl_forward_dynamics[_wrench]_backward: a again and -lambda = -M^-1 grad_accel, then the inertia contraction at
-// (q, v, a) with the cotangent -lambda on the same tree slots.
-int32_t nbl_forward_dynamics_backward_inertia(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* tau,
-                                              const double* wrench, int32_t flags, const double* grad_accel, double* grad_params,
-                                              int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  int32_t rc;
-  if (k) {
-    rc = wrenchCheck(m, k, B, state, grad_accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
-  } else {
-    rc = fdynCheck(m, B, state, grad_accel, workspace, workspace_bytes);
-    if (rc == NBL_OK) rc = dynFlags(flags);
-  }
-  if (rc != NBL_OK || B == 0 || m->nParams == 0) return rc;
-  if (!grad_params) return fail(NBL_E_BADARG, "null grad_params for " + std::to_string(m->nParams) + " registered inertia parameters");
-  DeviceGuard guard(m->device);
-  double* ws = (double*)workspace;
-  double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
-  double* neglam = accel + (size_t)m->n * (size_t)B;
-  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
-  if (k)
-    hipLaunchKernelGGL(k_forward_dynamics_wrench_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
-                       (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, grad_accel, accel, neglam,
-                       (double*)nullptr, 0, ws);
-  else
-    hipLaunchKernelGGL(k_forward_dynamics_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
-                       m->mdl, (int)flags, B, state, tau, grad_accel, accel, neglam, (double*)nullptr, 0, ws);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_inverse_dynamics_inertia_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, m->mdl,
-                     (int)(flags & DYN_FLAG_MASK), B, state, (const double*)accel, (const double*)neglam, (const DevInertiaParam*)m->dParams,
-                     m->nParams, grad_params, accumulate ? 1 : 0, ws);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
-                                     const double* wrench_guess, int32_t mode, int32_t flags, double* wrench_out, double* tau, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-  if (!k) return fail(NBL_E_BADARG, "null kinematics map: contact inverse dynamics needs at least one contact body");
-  if (mode != NBL_CID_SINGLE && mode != NBL_CID_NEAREST && mode != NBL_CID_MIN_TORQUE)
-    return fail(NBL_E_BADARG, "mode must be NBL_CID_SINGLE, NBL_CID_NEAREST or NBL_CID_MIN_TORQUE (got " + std::to_string(mode) + ")");
-  // (wrench_out stands in for the wrench array of the shared check: it is as long)
-  const int32_t rc = wrenchCheck(m, k, B, state, tau, wrench_out, flags, DYN_FLAG_MASK, workspace, workspace_bytes);
-  if (rc != NBL_OK) return rc;
-  if (mode == NBL_CID_SINGLE && k->count != 1)
-    return fail(NBL_E_BADARG, "NBL_CID_SINGLE takes one contact body (the set has " + std::to_string(k->count) + ")");
-  if (cidRoot(m->hBodies.data(), k->hEntries.data(), k->hPath.data(), k->count) < 0)
-    return fail(NBL_E_UNSUPPORTED, "contact inverse dynamics needs every contact body below ONE free joint at the root of its tree "
-                                   "(Skeleton::getContactInverseDynamics returns zeros otherwise)");
-  if (B == 0) return NBL_OK;
-  if (mode == NBL_CID_NEAREST && !wrench_guess) return fail(NBL_E_BADARG, "NBL_CID_NEAREST needs wrench_guess");
-  if (!accel) return fail(NBL_E_BADARG, "null argument");
-  DeviceGuard guard(m->device);
-  double* ws = (double*)workspace;
-  double* xs = ws + ((size_t)m->nb * (FD_SLOTS + 3) + 2 * (size_t)m->n) * (size_t)B;
-  hipLaunchKernelGGL(k_contact_inverse_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, (int)mode, B, state, accel, NBL_WRENCH_SET(k),
-                     mode == NBL_CID_NEAREST ? wrench_guess : (const double*)nullptr, wrench_out, tau, ws, xs);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-// ---- batched inverse kinematics (IKMapping::setPositions = math::solveIK with one restart; csrc/ik.hip) ---------------------------------
-void nbl_ik_default_config(nbl_ik_config* c) {   // math::IKConfig (IKSolver.hpp:31-38)
-  if (!c) return;
-  c->convergence_threshold = 1e-7; c->max_step_count = 100; c->least_squares_damping = 0.01;
-  c->start_clamped = 0; c->line_search = 1; c->dont_exit_transpose = 0;
-}
-
-size_t nbl_ik_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) {
-  if (!m || !k || B <= 0) return 0;
-  return sizeof(double) * (size_t)ikLayout(m->n, k->P).total * (size_t)B;
-}
-
-int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* target, const double* q_init, const nbl_ik_config* config,
-                     double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m || !k) return fail(NBL_E_BADARG, "null argument");
-  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  IkConfig cfg;
-  if (config) {
-    cfg.convergenceThreshold = config->convergence_threshold; cfg.maxStepCount = config->max_step_count;
-    cfg.damping = config->least_squares_damping; cfg.startClamped = config->start_clamped ? 1 : 0;
-    cfg.lineSearch = config->line_search ? 1 : 0; cfg.dontExitTranspose = config->dont_exit_transpose ? 1 : 0;
-  } else {   // IKMapping::setPositions: IKConfig().setMaxStepCount(500)
-    cfg.convergenceThreshold = 1e-7; cfg.maxStepCount = 500; cfg.damping = 0.01; cfg.startClamped = 0; cfg.lineSearch = 1; cfg.dontExitTranspose = 0;
-  }
-  if (cfg.maxStepCount < 1) return fail(NBL_E_BADARG, "max_step_count must be at least 1 (got " + std::to_string(cfg.maxStepCount) + ")");
-  if (cfg.maxStepCount > IK_MAX_STEP_COUNT)
-    return fail(NBL_E_BADARG, "max_step_count above " + std::to_string(IK_MAX_STEP_COUNT) + " (got " + std::to_string(cfg.maxStepCount) +
-                                  "): a lane runs its world's whole solve in one launch");
-  if (!(cfg.damping >= 0.0) || !(cfg.convergenceThreshold >= 0.0)) return fail(NBL_E_BADARG, "least_squares_damping and convergence_threshold must not be negative");
-  if (cfg.damping == 0.0)
-    return fail(NBL_E_UNSUPPORTED, "least_squares_damping = 0 (the reference's complete orthogonal decomposition) is outside the device path");
-  if (B == 0) return NBL_OK;
-  if (!target || !q_out || !workspace) return fail(NBL_E_BADARG, "null argument");
-  if ((B + IK_BLOCK - 1) / IK_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = nbl_ik_workspace_bytes(m, k, B);
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "IK workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_ik_workspace_bytes() = " + std::to_string(need));
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_ik_solve, dim3((unsigned)((B + IK_BLOCK - 1) / IK_BLOCK)), dim3(IK_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
-                     m->nb, m->n, k->P, B, target, q_init, cfg, q_out, loss, steps, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
 // ---- read-out of a step's contacts, impulses and body contact wrenches from its saved record (csrc/contact_readout.hip) --------------------
 static_assert(CO_POINT == NBL_CO_POINT && CO_NORMAL == NBL_CO_NORMAL && CO_DEPTH == NBL_CO_DEPTH && CO_TYPE == NBL_CO_TYPE &&
               CO_COLLIDER_A == NBL_CO_COLLIDER_A && CO_COLLIDER_B == NBL_CO_COLLIDER_B && CO_BODY_A == NBL_CO_BODY_A &&
@@ -2295,182 +1761,15 @@ int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, in
   return NBL_OK;
 }
 
-// ---- centre of mass, momentum and energy of a body set (csrc/centroidal.hip) -----------------------------------------------------------------
-struct nbl_body_set {
-  int device = 0, n = 0, nb = 0;   // the model it was made for
-  DevBodySet set{};
-};
-
-int32_t nbl_body_set_create(nbl_model* m, int32_t count, const int32_t* bodies, nbl_body_set** out) {
-  if (!m || !out) return fail(NBL_E_BADARG, "null argument");
-  *out = nullptr;
-  if (count < 0 || (count > 0 && !bodies)) return fail(NBL_E_BADARG, "a body set needs `count` body indices (or none: every body)");
-  if (m->nb > CEN_MAX_BODIES)
-    return fail(NBL_E_UNSUPPORTED, "body sets are masks over at most " + std::to_string(CEN_MAX_BODIES) + " internal bodies; the model has " + std::to_string(m->nb));
-  DevBodySet set{};
-  auto add = [&](int body) {
-    int i = m->deviceBody(body);
-    set.mass |= 1ull << i;
-    set.joints |= 1ull << i;
-    // the whole chain of a ball joint / a free joint below the root: its coordinates sit on the bodies before the one that carries T_cj
-    while ((m->hBodies[i].jtype == JT_BALL || m->hBodies[i].jtype == JT_FREEC) && m->hBodies[i].ballComp > 0) {
-      i = m->hBodies[i].parent;
-      set.joints |= 1ull << i;
-    }
-  };
-  if (count == 0) {
-    for (int i = 0; i < m->userBodies; i++) add(i);
-  } else {
-    for (int k = 0; k < count; k++) {
-      if (bodies[k] < 0 || bodies[k] >= m->userBodies)
-        return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": body " + std::to_string(bodies[k]) + " out of range [0, " + std::to_string(m->userBodies) + ")");
-      for (int f = 0; f < k; f++)
-        if (bodies[f] == bodies[k]) return fail(NBL_E_BADARG, "body " + std::to_string(bodies[k]) + " is named twice (entries " + std::to_string(f) + " and " + std::to_string(k) + ")");
-      add(bodies[k]);
-    }
-  }
-  if (!(cenTotalMass(m->hBodies.data(), m->nb, set.mass) > 0.0)) return fail(NBL_E_BADARG, "the body set has no mass");
-  nbl_body_set* s = new nbl_body_set();
-  s->device = m->device; s->n = m->n; s->nb = m->nb; s->set = set;
-  *out = s;
-  return NBL_OK;
-}
-
-void nbl_body_set_destroy(nbl_body_set* s) { delete s; }
-
-int32_t nbl_body_set_origin_moments(nbl_model* m, nbl_body_set* s, int32_t count, const int32_t* bodies, const double* moments) {
-  if (!m || !s || count < 0 || (count > 0 && (!bodies || !moments))) return fail(NBL_E_BADARG, "null argument");
-  if (s->n != m->n || s->nb != m->nb || s->device != m->device) return fail(NBL_E_BADARG, "the body set was made for another model");
-  for (int k = 0; k < count; k++) {
-    if (bodies[k] < 0 || bodies[k] >= m->userBodies) return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": body out of range");
-    for (int c = 0; c < 3; c++)
-      if (!std::isfinite(moments[3 * k + c])) return fail(NBL_E_BADARG, "entry " + std::to_string(k) + ": non-finite moment");
-  }
-  for (int k = 0; k < count; k++)
-    for (int c = 0; c < 3; c++) s->set.originMoment[3 * m->deviceBody(bodies[k]) + c] = moments[3 * k + c];
-  return NBL_OK;
-}
-
-double nbl_body_set_mass(nbl_model* m, const nbl_body_set* s) {
-  if (!m || !s) { (void)fail(NBL_E_BADARG, "null argument"); return 0.0; }
-  if (s->n != m->n || s->nb != m->nb || s->device != m->device) { (void)fail(NBL_E_BADARG, "the body set was made for another model"); return 0.0; }
-  return cenTotalMass(m->hBodies.data(), m->nb, s->set.mass);
-}
-
-size_t nbl_centroidal_workspace_bytes(const nbl_model* m, int64_t B) {
-  if (!m || B <= 0) return 0;
-  return sizeof(double) * (size_t)m->nb * CEN_SLOTS * (size_t)B;
-}
-
-static int32_t cenCheck(const nbl_model* m, const nbl_body_set* s, int64_t B, const double* state, int32_t flags, const void* workspace,
-                        size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (!s) return fail(NBL_E_BADARG, "null body set");
-  if (s->n != m->n || s->nb != m->nb || s->device != m->device) return fail(NBL_E_BADARG, "the body set was made for another model");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (flags & ~CEN_FLAG_MASK) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~CEN_FLAG_MASK) + " (NBL_CEN_*)");
-  if (B == 0) return NBL_OK;
-  if (!state) return fail(NBL_E_BADARG, "null argument");
-  if ((B + CEN_BLOCK - 1) / CEN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  if (!(cenTotalMass(m->hBodies.data(), m->nb, s->set.mass) > 0.0)) return fail(NBL_E_BADARG, "the body set has no mass");
-  const size_t need = nbl_centroidal_workspace_bytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "centroidal workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_centroidal_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
-}
-
-int32_t nbl_centroidal_forward(nbl_model* m, const nbl_body_set* set, int64_t B, const double* state, const double* accel, int32_t flags,
-                               double* com, double* com_vel, double* com_acc, double* momentum, double* ke, double* pe, double* Jcom,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = cenCheck(m, set, B, state, flags, workspace, workspace_bytes);
-  if (rc != NBL_OK) return rc;
-  if (com_acc && !accel) return fail(NBL_E_BADARG, "com_acc needs the accelerations (accel is null)");
-  if (B == 0 || !(com || com_vel || com_acc || momentum || ke || pe || Jcom)) return NBL_OK;
-  DeviceGuard guard(m->device);
-  hipStream_t s = (hipStream_t)stream;
-  m->timingNow = m->timing;
-  TIMED(K_CENTROIDAL, hipLaunchKernelGGL(k_centroidal, dim3((unsigned)((B + CEN_BLOCK - 1) / CEN_BLOCK)), dim3(CEN_BLOCK), 0, s,
-                                         (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, set->set, (int)flags, B, state, accel, com,
-                                         com_vel, com_acc, momentum, ke, pe, Jcom, (double*)workspace));
-  m->timingNow = false;
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_centroidal_backward(nbl_model* m, const nbl_body_set* set, int64_t B, const double* state, const double* accel, int32_t flags,
-                                const double* g_com, const double* g_com_vel, const double* g_com_acc, const double* g_momentum,
-                                const double* g_ke, const double* g_pe, double* grad_state, double* grad_accel, int32_t accumulate,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = cenCheck(m, set, B, state, flags, workspace, workspace_bytes);
-  if (rc != NBL_OK) return rc;
-  if (g_com_acc && !accel) return fail(NBL_E_BADARG, "g_com_acc needs the accelerations (accel is null)");
-  if (B == 0 || (!grad_state && !grad_accel)) return NBL_OK;
-  DeviceGuard guard(m->device);
-  hipStream_t s = (hipStream_t)stream;
-  m->timingNow = m->timing;
-  TIMED(K_CENTROIDAL_VJP, hipLaunchKernelGGL(k_centroidal_vjp, dim3((unsigned)((B + CEN_BLOCK - 1) / CEN_BLOCK)), dim3(CEN_BLOCK), 0, s,
-                                             (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, set->set, (int)flags, B, state, accel,
-                                             g_com, g_com_vel, g_com_acc, g_momentum, g_ke, g_pe, grad_state, grad_accel, accumulate ? 1 : 0,
-                                             (double*)workspace));
-  m->timingNow = false;
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-// ---- gyroscope, accelerometer and magnetometer readings of a sensor set (csrc/sensors.hip) ---------------------------------------------------
-size_t nbl_sensors_workspace_bytes(const nbl_model* m, int64_t B) { return nbl_centroidal_workspace_bytes(m, B); }
-
-// the checks the two sensor calls share; a sensor set is a kinematics map of NBL_KIN_SPATIAL entries, like a wrench set
-static int32_t sensCheck(const nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (!k) return fail(NBL_E_BADARG, "null sensor set");
-  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  for (int e = 0; e < k->count; e++)
-    if (k->hEntries[e].kind != KIN_SPATIAL)
-      return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the sensor set is not NBL_KIN_SPATIAL: a sensor needs a whole frame");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (B == 0) return NBL_OK;
-  if (!state) return fail(NBL_E_BADARG, "null argument");
-  if ((B + SENS_BLOCK - 1) / SENS_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = nbl_sensors_workspace_bytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "sensor workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_sensors_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
-}
-
-int32_t nbl_sensors_forward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
-                            double* gyro, double* acc, double* mag, void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = sensCheck(m, k, B, state, workspace, workspace_bytes);
-  if (rc != NBL_OK) return rc;
-  if (acc && !accel) return fail(NBL_E_BADARG, "acc needs the accelerations (accel is null)");
-  if (mag && !field) return fail(NBL_E_BADARG, "mag needs the magnetic field (field is null)");
-  if (B == 0 || !(gyro || acc || mag)) return NBL_OK;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_sensors, dim3((unsigned)((B + SENS_BLOCK - 1) / SENS_BLOCK)), dim3(SENS_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, B, state, accel, field,
-                     gyro, acc, mag, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
-int32_t nbl_sensors_backward(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
-                             const double* g_gyro, const double* g_acc, const double* g_mag, double* grad_state, double* grad_accel,
-                             double* grad_field, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  const int32_t rc = sensCheck(m, k, B, state, workspace, workspace_bytes);
-  if (rc != NBL_OK) return rc;
-  if (g_acc && !accel) return fail(NBL_E_BADARG, "g_acc needs the accelerations (accel is null)");
-  if (g_mag && !field) return fail(NBL_E_BADARG, "g_mag needs the magnetic field (field is null)");
-  if (B == 0 || (!grad_state && !grad_accel && !grad_field)) return NBL_OK;
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_sensors_vjp, dim3((unsigned)((B + SENS_BLOCK - 1) / SENS_BLOCK)), dim3(SENS_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, B, state, accel, field,
-                     g_gyro, g_acc, g_mag, grad_state, grad_accel, grad_field, accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
-
 }  // extern "C"
+
+// The contact-independent calls (kinematics, dynamics, IK, centroidal quantities, sensors) live in nimble_amd_tree.hip and work on the
+// capacity-independent base of a handle.
+#ifdef NBL_VARIANT_SUFFIX
+// one unit, built once, serves every instantiation: the dispatcher fetches the base once per model through this accessor
+extern "C" nbl_tree_model* nbl_model_tree(nbl_model* m) { return m; }
+#else
+// the stand-alone build is the whole library: the same calls on this file's own handle, with this file's error text
+#define NBL_TREE_STANDALONE
+#include "nimble_amd_tree.hip"
+#endif

@@ -1,6 +1,8 @@
-"""The inverse-kinematics entry points exist in EVERY build of the library: nimble_amd.hip alone is the whole library in its 8-contact
-form (csrc/abi_variants.h; the developer builds of tools/ compile it that way and load it through NBL_LIB_PATH), so every function
-include/nimble_amd.h declares - nbl_ik_default_config included - is defined there and renamed per instantiation, not in the dispatcher only."""
+"""Every function include/nimble_amd.h declares - nbl_ik_default_config included - exists in EVERY build of the library, and in exactly one
+place.  The calls that depend on the contact capacity are defined in nimble_amd.hip and renamed per instantiation (csrc/abi_variants.h); the
+contact-independent ones (kinematics, dynamics, IK, centroidal, sensors) are defined once, in nimble_amd_tree.hip, under their public names:
+never renamed, never in the dispatcher's table.  nimble_amd.hip alone, which then includes nimble_amd_tree.hip, is the whole library in its
+8-contact form (the developer builds of tools/ compile it that way and load it through NBL_LIB_PATH)."""
 import os
 import re
 
@@ -14,11 +16,28 @@ def _extern_c(text):
     return text[text.index('extern "C" {'):]
 
 
+def _defines(sym, src):
+    return re.search(r"^[a-z_0-9 *]*\b%s\s*\(" % sym, src, re.M) is not None
+
+
 def test_every_public_symbol_is_defined_in_the_single_unit_library():
-    src = _extern_c(open(os.path.join(CSRC, "nimble_amd.hip")).read())
+    per_capacity = _extern_c(open(os.path.join(CSRC, "nimble_amd.hip")).read())
+    once = _extern_c(open(os.path.join(CSRC, "nimble_amd_tree.hip")).read())
     renamed = set(re.findall(r"#define (nbl_[a-z0-9_]+) NBL_V", open(os.path.join(CSRC, "abi_variants.h")).read()))
+    disp = open(os.path.join(CSRC, "nimble_amd_dispatch.cpp")).read()
+    n_once = 0
     for sym in _lib.EXPORTED_SYMBOLS:
-        assert re.search(r"^[a-z_0-9 *]*\b%s\s*\(" % sym, src, re.M), f"{sym} is not defined in nimble_amd.hip"
-        assert sym in renamed, f"{sym} is not renamed per instantiation in abi_variants.h"
+        in_hip, in_tree = _defines(sym, per_capacity), _defines(sym, once)
+        assert in_hip != in_tree, f"{sym} must be defined in nimble_amd.hip or in nimble_amd_tree.hip, and in one of them only"
+        if in_hip:
+            assert sym in renamed, f"{sym} is not renamed per instantiation in abi_variants.h"
+        else:
+            n_once += 1
+            assert sym not in renamed, f"{sym} is built once (nimble_amd_tree.hip) but renamed in abi_variants.h"
+            assert sym + "##S" not in disp and "(*%s)" % sym[4:] not in disp and not _defines(sym, disp), \
+                f"{sym} is built once but still passes through the dispatcher"
+    assert n_once == 35
+    # the stand-alone library (nimble_amd.hip without NBL_VARIANT_SUFFIX) takes the rest from the same file
+    assert re.search(r'^#else\n(//[^\n]*\n)*#define NBL_TREE_STANDALONE\n#include "nimble_amd_tree.hip"\n#endif', per_capacity, re.M)
     for sym in ("nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve"):
         assert sym in _lib.EXPORTED_SYMBOLS
