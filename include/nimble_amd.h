@@ -858,6 +858,36 @@ int32_t nbl_kernel_count(void);
 const char* nbl_kernel_name(int32_t i);
 int32_t nbl_kernel_timing(nbl_model* m, int32_t i, double* ms_sum, int64_t* count);
 
+/* ---- task-space Jacobians, their time derivative and task-space accelerations (csrc/taskspace.hip) ---------------------------------------------
+ * Second-order world-space kinematics of the rows of a kinematics map, entries of any kind (the rows, their order and their frames are those of
+ * nbl_kinematics_forward's vel), for B worlds: BodyNode::getJacobian / getJacobianClassicDeriv / getLinearJacobianDeriv /
+ * getAngularJacobianDeriv of the reference, batched.  With R = nbl_kin_map_dim(k) and n the DOFs:
+ *   J    [R n][B]  row-major R x n per world: vel = J v.  One pass per entry, every column written (zero where a coordinate is no ancestor's).
+ *   Jdot [R n][B]  d/dt J along the motion (q moving with v), so that Jdot v = bias.  Forward only.
+ *   bias [R][B]    Jdot v
+ *   xdd  [R][B]    J accel + Jdot v: for linear rows the classical acceleration of the frame's origin, for angular rows the angular
+ *                  acceleration, each the time derivative of the vel row; ball and free joints carry their Sdot v term.  No gravity.
+ * nbl_task_accel writes bias and / or xdd (either may be NULL; xdd needs accel).
+ * nbl_task_jacobian_vjp: grad_q [n][B] = (accumulate: +=) d<G, J>/dq for a cotangent G [R n][B], exactly.
+ * nbl_task_accel_vjp: grad_state [2n][B] and grad_accel [n][B] (either may be NULL) = (accumulate: +=) the cotangent g_out [R][B] of xdd -
+ * accel NULL: of bias - pulled back exactly; the dependence of J accel + Jdot v on q is included.
+ * `rows` and `n` are the caller's R and n, checked against the map and the model: NBL_E_BADARG on a mismatch, as on a null handle, map,
+ * state or required output, a map made for another model, B < 0; NBL_E_WORKSPACE.  B = 0 is a no-op.  All pointers are device pointers, SoA,
+ * state [2n][B] = [q; v], accel [n][B].  Only nbl_task_accel_vjp needs a workspace: nbl_task_workspace_bytes(m, B) bytes of device scratch
+ * (54 doubles per body and world).  Stream-ordered on `stream`, no synchronisation, no atomics, no LDS: bit-reproducible and independent
+ * of B and of a world's place in the batch; B may be (T + 1) x worlds.  The calls do not use the handle's slices. */
+size_t nbl_task_workspace_bytes(const nbl_model* m, int64_t B);
+int32_t nbl_task_jacobian(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream);
+int32_t nbl_task_accel(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+                       double* bias, double* xdd, void* stream);
+int32_t nbl_task_accel_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+                           const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int32_t nbl_task_jacobian_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
+                              double* grad_q, int32_t accumulate, void* stream);
+int32_t nbl_task_jacobian_deriv(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

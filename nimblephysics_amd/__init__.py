@@ -15,7 +15,8 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "rollout_body_contact_wrenches", "ContactReadout", "center_of_mass", "com_velocity", "com_acceleration", "centroidal_momentum",
            "kinetic_energy", "potential_energy", "com_jacobian", "centroidal", "Centroidal", "gyro_readings", "accelerometer_readings",
            "magnetometer_readings", "imu_readings", "IMUReadings", "gyro_jacobian", "accelerometer_jacobian", "magnetometer_jacobian",
-           "inverse_dynamics_mass_gradient", "forward_dynamics_mass_gradient", "inverse_dynamics_mass_jacobian", "forward_dynamics_mass_jacobian"]
+           "inverse_dynamics_mass_gradient", "forward_dynamics_mass_gradient", "inverse_dynamics_mass_jacobian", "forward_dynamics_mass_jacobian",
+           "task_jacobian", "task_jacobian_dot_times_v", "map_to_acc", "task_jacobian_deriv"]
 
 
 def __getattr__(name):
@@ -62,6 +63,9 @@ def __getattr__(name):
                 "accelerometer_jacobian", "magnetometer_jacobian"):
         from . import sensors as _s
         return getattr(_s, name)
+    if name in ("task_jacobian", "task_jacobian_dot_times_v", "map_to_acc", "task_jacobian_deriv"):
+        from . import taskspace as _ts
+        return getattr(_ts, name)
     if name in ("timestep", "TimestepLayer", "rollout", "RolloutLayer"):
         from . import timestep as _t
         return getattr(_t, name)

@@ -190,6 +190,17 @@ def lib():
     L.nbl_inverse_dynamics_backward_inertia.restype = C.c_int32
     L.nbl_forward_dynamics_backward_inertia.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_size_t, vp]
     L.nbl_forward_dynamics_backward_inertia.restype = C.c_int32
+    L.nbl_task_workspace_bytes.argtypes = [vp, C.c_int64]
+    L.nbl_task_workspace_bytes.restype = C.c_size_t
+    for f in ("nbl_task_jacobian", "nbl_task_jacobian_deriv"):
+        getattr(L, f).argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
+        getattr(L, f).restype = C.c_int32
+    L.nbl_task_jacobian_vjp.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
+    L.nbl_task_jacobian_vjp.restype = C.c_int32
+    L.nbl_task_accel.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    L.nbl_task_accel.restype = C.c_int32
+    L.nbl_task_accel_vjp.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp]
+    L.nbl_task_accel_vjp.restype = C.c_int32
     _lib = L
     return L
 
@@ -212,6 +223,7 @@ EXPORTED_SYMBOLS = [
     "nbl_body_set_create", "nbl_body_set_destroy", "nbl_body_set_mass", "nbl_body_set_origin_moments", "nbl_centroidal_workspace_bytes", "nbl_centroidal_forward", "nbl_centroidal_backward",
     "nbl_sensors_workspace_bytes", "nbl_sensors_forward", "nbl_sensors_backward",
     "nbl_inverse_dynamics_backward_inertia", "nbl_forward_dynamics_backward_inertia",
+    "nbl_task_workspace_bytes", "nbl_task_jacobian", "nbl_task_accel", "nbl_task_accel_vjp", "nbl_task_jacobian_vjp", "nbl_task_jacobian_deriv",
 ]
 
 

@@ -79,7 +79,14 @@
 #define nbl_contact_readout NBL_V(nbl_contact_readout)
 #define nbl_contact_readout_rows NBL_V(nbl_contact_readout_rows)
 #define nbl_contact_body_wrenches NBL_V(nbl_contact_body_wrenches)
-#define nbl_model_tree NBL_V(nbl_model_tree)   /* (not in the ABI: the handle's base for nimble_amd_tree.hip, tree_model_host.hpp) */
+/* the task-space entries: per instantiation only as thin forwards; their kernels are built once (nimble_amd_tree.hip, tree_model_host.hpp) */
+#define nbl_task_workspace_bytes NBL_V(nbl_task_workspace_bytes)
+#define nbl_task_jacobian NBL_V(nbl_task_jacobian)
+#define nbl_task_jacobian_deriv NBL_V(nbl_task_jacobian_deriv)
+#define nbl_task_jacobian_vjp NBL_V(nbl_task_jacobian_vjp)
+#define nbl_task_accel NBL_V(nbl_task_accel)
+#define nbl_task_accel_vjp NBL_V(nbl_task_accel_vjp)
+#define nbl_model_tree NBL_V(nbl_model_tree)  /* (not in the ABI: the handle's base for nimble_amd_tree.hip, tree_model_host.hpp) */
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */
 #undef NBL_E_CAPACITY

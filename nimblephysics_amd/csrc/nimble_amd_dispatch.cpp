@@ -4,6 +4,7 @@
 // contacts = 192 LCP rows, 64 colliders, 512 pairs: rows looped over instead of mapped to lanes - there so that no legal world
 // gets a truncated answer; 2 M world-steps/s on eight-contact worlds since round 6; a fourth instantiation is the same code with 384 rows); every later call that exists per capacity goes to the build that owns the handle.
 // The contact-independent calls are not dispatched: nimble_amd_tree.hip defines them once, over the handle's base (dispatch_handle.hpp).
+// The task-space entries are routed here, but every instantiation only forwards them to that one build (tree_model_host.hpp).
 // Host code only; no HIP call of its own.
 #include <cstddef>
 #include <cstdint>
@@ -74,6 +75,14 @@
   int32_t nbl_contact_readout##S(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);                              \
   int32_t nbl_contact_readout_rows##S(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);                                   \
   int32_t nbl_contact_body_wrenches##S(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);                              \
+  size_t nbl_task_workspace_bytes##S(const void*, int64_t);                                                                                \
+  int32_t nbl_task_jacobian##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);                       \
+  int32_t nbl_task_jacobian_deriv##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);                 \
+  int32_t nbl_task_jacobian_vjp##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, int32_t,   \
+                                   void*);                                                                                                 \
+  int32_t nbl_task_accel##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, double*, void*);  \
+  int32_t nbl_task_accel_vjp##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, const double*,         \
+                                double*, double*, int32_t, void*, size_t, void*);                                                          \
   nbl_tree_model* nbl_model_tree##S(void*);
 
 extern "C" {
@@ -128,6 +137,13 @@ struct Variant {
   int32_t (*contact_readout)(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);
   int32_t (*contact_readout_rows)(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);
   int32_t (*contact_body_wrenches)(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);
+  size_t (*task_workspace_bytes)(const void*, int64_t);
+  int32_t (*task_jacobian)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);
+  int32_t (*task_jacobian_deriv)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);
+  int32_t (*task_jacobian_vjp)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, int32_t, void*);
+  int32_t (*task_accel)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, double*, void*);
+  int32_t (*task_accel_vjp)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, const double*, double*, double*, int32_t,
+                            void*, size_t, void*);
   nbl_tree_model* (*model_tree)(void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
@@ -139,7 +155,8 @@ struct Variant {
    nbl_selftest_lcp_dantzig_timed##S, nbl_selftest_pinv_rows##S, nbl_set_launch_lanes##S, nbl_set_slices##S, nbl_slices_for##S,               \
    nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
    nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_contact_readout##S, nbl_contact_readout_rows##S,          \
-   nbl_contact_body_wrenches##S, nbl_model_tree##S}
+   nbl_contact_body_wrenches##S, nbl_task_workspace_bytes##S, nbl_task_jacobian##S, nbl_task_jacobian_deriv##S, nbl_task_jacobian_vjp##S,       \
+   nbl_task_accel##S, nbl_task_accel_vjp##S, nbl_model_tree##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -344,6 +361,31 @@ int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int
 }
 int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream) {
   return NBL_FWD(m, contact_body_wrenches, B, saved, E, bodies, wrench, stream);
+}
+
+// ---- task-space Jacobians and accelerations: every instantiation forwards to the one build of nimble_amd_tree.hip, which reports its
+// refusals through ownError like the contact-independent calls (so not NBL_FWD: the text is the dispatcher's own) ----
+#define NBL_TASK(m, FN, ...) (!(m) ? ownError(NBL_E_BADARG, "null model") : (m)->v->FN((m)->impl, ##__VA_ARGS__))
+size_t nbl_task_workspace_bytes(const nbl_model* m, int64_t B) { return NBL_GET(m, task_workspace_bytes, B); }
+int32_t nbl_task_jacobian(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream) {
+  return NBL_TASK(m, task_jacobian, k, B, rows, n, state, J, stream);
+}
+int32_t nbl_task_jacobian_deriv(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
+                                void* stream) {
+  return NBL_TASK(m, task_jacobian_deriv, k, B, rows, n, state, Jdot, stream);
+}
+int32_t nbl_task_jacobian_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
+                              double* grad_q, int32_t accumulate, void* stream) {
+  return NBL_TASK(m, task_jacobian_vjp, k, B, rows, n, state, G, grad_q, accumulate, stream);
+}
+int32_t nbl_task_accel(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+                       double* bias, double* xdd, void* stream) {
+  return NBL_TASK(m, task_accel, k, B, rows, n, state, accel, bias, xdd, stream);
+}
+int32_t nbl_task_accel_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+                           const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return NBL_TASK(m, task_accel_vjp, k, B, rows, n, state, accel, g_out, grad_state, grad_accel, accumulate, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // nimble_amd_tree.hip — the contact-independent entry points of include/nimble_amd.h: world-space kinematics, inverse and forward dynamics,
-// mass matrix and its inverse, wrenches, contact inverse dynamics, inertia-parameter gradients, IK, centroidal quantities and sensors.
+// mass matrix and its inverse, wrenches, contact inverse dynamics, inertia-parameter gradients, IK, centroidal quantities, sensors and
+// task-space Jacobians and accelerations.
 //
 // None of them depends on the contact capacity, so they are built ONCE (device namespace nbl_tree) and not once per instantiation of the
 // contact stage (abi_variants.h): every call works on the capacity-independent base of the handle, nbl_tree_model (tree_model_host.hpp),
@@ -25,6 +26,7 @@ static int fail(int code, const std::string& msg) { return ownError(code, msg.c_
 #include "dynamics.hip"
 #include "centroidal.hip"
 #include "sensors.hip"
+#include "taskspace.hip"
 #include "ik.hip"
 
 using namespace NBL_NS;
@@ -759,3 +761,96 @@ int32_t nbl_sensors_backward(nbl_model* h, const nbl_kin_map* k, int64_t B, cons
 }
 
 }  // extern "C"
+
+// ---- task-space Jacobians, their time derivative and task-space accelerations (csrc/taskspace.hip) ------------------------------------------
+// The kernels are built once, here; the entry points nbl_task_* of include/nimble_amd.h exist per instantiation (nimble_amd.hip, renamed by
+// abi_variants.h, routed by the dispatcher) as thin forwards to the functions below on the handle's base (tree_model_host.hpp declares them).
+size_t treeTaskWorkspaceBytes(const nbl_tree_model* m, int64_t B) { return cenWorkspaceBytes(m, B); }
+
+// the checks the five calls share
+static int32_t taskCheck(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (!k) return fail(NBL_E_BADARG, "null kinematics map");
+  if (k->capacity != m->capacity || k->n != m->n || k->nb != m->nb || k->device != m->device)
+    return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  if (rows != k->P) return fail(NBL_E_BADARG, "rows = " + std::to_string(rows) + ", the kinematics map has " + std::to_string(k->P));
+  if (n != m->n) return fail(NBL_E_BADARG, "n = " + std::to_string(n) + ", the model has " + std::to_string(m->n) + " DOFs");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (B == 0) return NBL_OK;
+  if (!state) return fail(NBL_E_BADARG, "null argument");
+  if ((B + TASK_BLOCK - 1) / TASK_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  return NBL_OK;
+}
+#define TASK_GRID(B) dim3((unsigned)(((B) + TASK_BLOCK - 1) / TASK_BLOCK)), dim3(TASK_BLOCK), 0, (hipStream_t)stream
+
+int32_t treeTaskJacobian(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream) {
+  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  if (rc != NBL_OK) return rc;
+  if (B == 0) return NBL_OK;
+  if (!J) return fail(NBL_E_BADARG, "null argument");
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_task_jacobian, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
+                     m->n, B, state, J);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t treeTaskJacobianDeriv(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
+                                void* stream) {
+  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  if (rc != NBL_OK) return rc;
+  if (B == 0) return NBL_OK;
+  if (!Jdot) return fail(NBL_E_BADARG, "null argument");
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_task_jacobian_deriv, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath,
+                     k->count, m->n, B, state, Jdot);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t treeTaskJacobianVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
+                              double* grad_q, int32_t accumulate, void* stream) {
+  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  if (rc != NBL_OK) return rc;
+  if (B == 0) return NBL_OK;
+  if (!G || !grad_q) return fail(NBL_E_BADARG, "null argument");
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_task_jacobian_vjp, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath,
+                     k->count, m->n, B, state, G, grad_q, accumulate ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t treeTaskAccel(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+                       double* bias, double* xdd, void* stream) {
+  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  if (rc != NBL_OK) return rc;
+  if (xdd && !accel) return fail(NBL_E_BADARG, "xdd needs the accelerations (accel is null)");
+  if (B == 0 || (!bias && !xdd)) return NBL_OK;
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_task_accel, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
+                     m->n, B, state, accel, bias, xdd);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+
+int32_t treeTaskAccelVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+                           const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  if (rc != NBL_OK) return rc;
+  if (grad_accel && !accel) return fail(NBL_E_BADARG, "grad_accel needs the accelerations (accel is null)");
+  if (B == 0 || (!grad_state && !grad_accel)) return NBL_OK;
+  if (!g_out) return fail(NBL_E_BADARG, "null argument");
+  const size_t need = cenWorkspaceBytes(m, B);   // (= nbl_task_workspace_bytes)
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "task-space workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_task_workspace_bytes() = " + std::to_string(need));
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_task_accel_vjp, TASK_GRID(B), (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath,
+                     k->count, B, state, accel, g_out, grad_state, grad_accel, accumulate ? 1 : 0, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}
+#undef TASK_GRID

@@ -196,6 +196,23 @@ class IKMapping:
         """IKMapping::getRealVelToMappedVelJac = getVelJacobian (IKMapping.cpp:429-473): [B, P, n], dense."""
         return self._dense(world, 1)
 
+    # ---- second order, on the World's current state (taskspace.py; one pass of csrc/taskspace.hip, detached) ----
+    def getJacobian(self, world) -> torch.Tensor:
+        """[B, P, n]: the velocity Jacobian, getVelocities = J v.  Agrees with getRealVelToMappedVelJac, without its P reverse-mode worlds."""
+        from .taskspace import current_jacobian
+        return current_jacobian(world, self, False)
+
+    def getJacobianDeriv(self, world) -> torch.Tensor:
+        """[B, P, n]: d/dt of getJacobian along the motion of the World's state."""
+        from .taskspace import current_jacobian
+        return current_jacobian(world, self, True)
+
+    def getAccelerations(self, world, accelerations: torch.Tensor) -> torch.Tensor:
+        """[B, P]: the time derivative of getVelocities at the joint accelerations [B, n] ([n] for a state set as one 1-D vector):
+        J accelerations + Jdot v, no gravity."""
+        from .taskspace import current_accelerations
+        return current_accelerations(world, self, accelerations)
+
     # ---- the reference's setters on the World's current state (IKMapping.cpp:86-135) ----
     def setPositions(self, world, positions: torch.Tensor):
         """IKMapping::setPositions: solve for joint positions whose mapped positions are `positions` ([B, P], or [P] for a state set as
