@@ -244,7 +244,9 @@ const char* nbl_last_error(void);
  *            + nbl_sensors_workspace_bytes, nbl_sensors_forward, nbl_sensors_backward (gyroscope, accelerometer and magnetometer readings
  *            of a sensor set, below: appended without a new minor number, like the entries above).
  *            + nbl_inverse_dynamics_backward_inertia, nbl_forward_dynamics_backward_inertia (gradients of the dynamics calls to the
- *            registered inertia parameters, below: appended without a new minor number, like the entries above). */
+ *            registered inertia parameters, below: appended without a new minor number, like the entries above).
+ *            + nbl_ik_grad_workspace_bytes, nbl_ik_solve_vjp (the reverse pass of the inverse kinematics, below: appended without a new
+ *            minor number, like the entries above - a caller that needs them looks the symbols up). */
 #define NBL_ABI_MINOR 5
 int32_t nbl_version(void);
 
@@ -690,7 +692,7 @@ int32_t nbl_contact_inverse_dynamics(nbl_model* m, const nbl_kin_map* k, int64_t
  * Errors: NBL_E_BADARG (null handle / map / target / q_out / workspace, B < 0, max_step_count < 1 or > 100000, negative damping or threshold),
  * NBL_E_WORKSPACE (workspace too small), NBL_E_UNSUPPORTED (damping = 0); nothing is launched then.  B = 0 is a no-op.  Stream-ordered
  * on `stream`, no synchronisation, no atomics; it does not use the handle's slices.  Results do not depend on B or on a world's place
- * in the batch.  No gradients flow through the solve (the reference has none). */
+ * in the batch.  The reference has no gradient of the solve; nbl_ik_solve_vjp below gives the one this library defines. */
 typedef struct {
   double convergence_threshold;   /* 1e-7 */
   int32_t max_step_count;         /* 100; IKMapping::setPositions passes 500 */
@@ -703,6 +705,30 @@ void nbl_ik_default_config(nbl_ik_config* config); /* math::IKConfig's defaults 
 size_t nbl_ik_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B);
 int32_t nbl_ik_solve(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* target, const double* q_init, const nbl_ik_config* config,
                      double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the reverse pass of inverse kinematics (csrc/ik_grad.hip) ---------------------------------------------------------------------------
+ * grad_target = (d q / d target)^T grad_q at the positions q nbl_ik_solve returned: what a loss on q contributes to the gradient of the
+ * targets.  The reference has no such gradient; this is the library's own convention.  Let J = IKMapping::getPosJacobian at q (the dense
+ * Jacobian the solver builds, the exact derivative nbl_kinematics_backward applies) and F the FREE coordinates: a coordinate is clamped
+ * when q_i equals a finite pos_lo_i or pos_hi_i bit for bit - what the solver's clamp leaves behind -, free otherwise (always, for an
+ * infinite limit).  With J_F the columns of J in F,
+ *     grad_target = J_F (J_F^T J_F + mu I)^-1 (grad_q)_F  =  (J_F J_F^T + mu I)^-1 J_F (grad_q)_F,
+ * the Gauss-Newton sensitivity of min |rows(q) - target|^2 over the free coordinates.  Clamped coordinates contribute nothing; with no
+ * free coordinate grad_target is 0.  mu = grad_damping > 0 is a Tikhonov term of the gradient alone (NOT the solver's
+ * least_squares_damping; 1e-9 is a good default); grad_damping = 0 is NBL_E_UNSUPPORTED, as the solver refuses damping 0.  The kernel
+ * factors the SMALLER of the two forms, min(P, |F|) <= 64 on a side, by the solver's in-place Cholesky and two triangular solves.
+ * Two limits of the convention:
+ *   1. the second-order term sum_k (rows(q) - target)_k grad^2 rows_k is left out: the result is the derivative of the solve where the
+ *      target is met (and the solve converged), and the Gauss-Newton approximation of it elsewhere;
+ *   2. there is no gradient with respect to q_init.
+ * q, grad_q [n][B], grad_target [P][B] (accumulate != 0: added to), free_count [B] int32 = |F| per world (may be NULL): DEVICE pointers,
+ * SoA.  workspace: nbl_ik_grad_workspace_bytes(m, k, B) bytes of device scratch (the solver's layout).  Errors: NBL_E_BADARG (null handle
+ * / map / q / grad_q / grad_target / workspace, B < 0, negative grad_damping), NBL_E_WORKSPACE (workspace too small), NBL_E_UNSUPPORTED
+ * (grad_damping = 0); nothing is launched then.  B = 0 is a no-op.  Stream-ordered on `stream`, no synchronisation, no atomics; it does
+ * not use the handle's slices.  Results are bit-reproducible and do not depend on B or on a world's place in the batch. */
+size_t nbl_ik_grad_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B);
+int32_t nbl_ik_solve_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
+                         double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- read-out of a step's contacts, impulses and body contact wrenches (csrc/contact_readout.hip) -----------------------------------------
  * What the contacts of a step WERE, decoded from its saved record (`saved`: the nbl_saved_bytes(m, B) bytes nbl_step_forward wrote; the T

@@ -10,7 +10,7 @@ __all__ = ["ModelDescription", "BodySpec", "BoxSpec", "SphereSpec", "CapsuleSpec
            "atlas", "box_stack", "make_transform", "load_urdf", "load_skel", "with_ground", "load_model", "loadWorld", "model_from_nimble_world", "WrtMassBodyNodeEntryType", "GraphedStep", "GraphedRollout", "neural", "forwardPass", "BackpropSnapshot",
            "LossGradient", "LossGradientHighLevelAPI", "NimbleAmdError", "IKMapping", "map_to_pos", "map_to_vel", "MapToPosLayer",
            "MapToVelLayer", "inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics",
-           "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "IKConfig", "contact_inverse_dynamics",
+           "multiply_by_inv_mass_matrix", "inv_mass_matrix", "solve_ik", "solve_ik_vjp", "SolveIKLayer", "IKConfig", "contact_inverse_dynamics",
            "inverse_dynamics_from_predictions", "read_contacts", "body_contact_wrenches", "rollout_contacts",
            "rollout_body_contact_wrenches", "ContactReadout", "center_of_mass", "com_velocity", "com_acceleration", "centroidal_momentum",
            "kinetic_energy", "potential_energy", "com_jacobian", "centroidal", "Centroidal", "gyro_readings", "accelerometer_readings",
@@ -43,7 +43,7 @@ def __getattr__(name):
     if name in ("World",):
         from .world import World
         return World
-    if name in ("IKMapping", "map_to_pos", "map_to_vel", "MapToPosLayer", "MapToVelLayer", "solve_ik", "IKConfig"):
+    if name in ("IKMapping", "map_to_pos", "map_to_vel", "MapToPosLayer", "MapToVelLayer", "solve_ik", "solve_ik_vjp", "SolveIKLayer", "IKConfig"):
         from . import mapping as _m
         return getattr(_m, name)
     if name in ("inverse_dynamics", "coriolis_and_gravity", "mass_matrix", "forward_dynamics", "multiply_by_inv_mass_matrix", "inv_mass_matrix",

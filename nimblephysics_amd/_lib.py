@@ -150,6 +150,10 @@ def lib():
     L.nbl_ik_workspace_bytes.restype = C.c_size_t
     L.nbl_ik_solve.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.nbl_ik_solve.restype = C.c_int32
+    L.nbl_ik_grad_workspace_bytes.argtypes = [vp, vp, C.c_int64]
+    L.nbl_ik_grad_workspace_bytes.restype = C.c_size_t
+    L.nbl_ik_solve_vjp.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_double, vp, C.c_int32, vp, vp, C.c_size_t, vp]
+    L.nbl_ik_solve_vjp.restype = C.c_int32
     L.nbl_wrench_workspace_bytes.argtypes = [vp, vp, C.c_int64]
     L.nbl_wrench_workspace_bytes.restype = C.c_size_t
     for f in ("nbl_inverse_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_forward"):
@@ -216,7 +220,7 @@ EXPORTED_SYMBOLS = [
     "nbl_kin_map_create", "nbl_kin_map_destroy", "nbl_kin_map_dim", "nbl_kinematics_forward", "nbl_kinematics_backward",
     "nbl_dynamics_workspace_bytes", "nbl_inverse_dynamics_forward", "nbl_inverse_dynamics_backward", "nbl_mass_matrix",
     "nbl_forward_dynamics_workspace_bytes", "nbl_forward_dynamics_forward", "nbl_forward_dynamics_backward", "nbl_inv_mass_apply", "nbl_inv_mass_matrix",
-    "nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve",
+    "nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve", "nbl_ik_grad_workspace_bytes", "nbl_ik_solve_vjp",
     "nbl_wrench_workspace_bytes", "nbl_inverse_dynamics_wrench_forward", "nbl_inverse_dynamics_wrench_backward",
     "nbl_forward_dynamics_wrench_forward", "nbl_forward_dynamics_wrench_backward", "nbl_contact_inverse_dynamics",
     "nbl_contact_readout", "nbl_contact_readout_rows", "nbl_contact_body_wrenches",

@@ -86,6 +86,9 @@
 #define nbl_task_jacobian_vjp NBL_V(nbl_task_jacobian_vjp)
 #define nbl_task_accel NBL_V(nbl_task_accel)
 #define nbl_task_accel_vjp NBL_V(nbl_task_accel_vjp)
+/* the reverse pass of IK: thin forwards like the task-space entries (kernel built once: csrc/ik_grad.hip) */
+#define nbl_ik_grad_workspace_bytes NBL_V(nbl_ik_grad_workspace_bytes)
+#define nbl_ik_solve_vjp NBL_V(nbl_ik_solve_vjp)
 #define nbl_model_tree NBL_V(nbl_model_tree)  /* (not in the ABI: the handle's base for nimble_amd_tree.hip, tree_model_host.hpp) */
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */

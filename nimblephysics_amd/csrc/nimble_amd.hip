@@ -1785,6 +1785,13 @@ int32_t nbl_task_accel_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_
   return treeTaskAccelVjp(m, k, B, rows, n, state, accel, g_out, grad_state, grad_accel, accumulate, workspace, workspace_bytes, stream);
 }
 
+// ---- the reverse pass of inverse kinematics (csrc/ik_grad.hip): built once like the task-space kernels, forwarded to like them ----
+size_t nbl_ik_grad_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) { return treeIkGradWorkspaceBytes(m, k, B); }
+int32_t nbl_ik_solve_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
+                         double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
+  return treeIkSolveVjp(m, k, B, q, grad_q, grad_damping, grad_target, accumulate, free_count, workspace, workspace_bytes, stream);
+}
+
 }  // extern "C"
 
 // The contact-independent calls (kinematics, dynamics, IK, centroidal quantities, sensors) live in nimble_amd_tree.hip and work on the

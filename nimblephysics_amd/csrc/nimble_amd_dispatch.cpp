@@ -4,7 +4,8 @@
 // contacts = 192 LCP rows, 64 colliders, 512 pairs: rows looped over instead of mapped to lanes - there so that no legal world
 // gets a truncated answer; 2 M world-steps/s on eight-contact worlds since round 6; a fourth instantiation is the same code with 384 rows); every later call that exists per capacity goes to the build that owns the handle.
 // The contact-independent calls are not dispatched: nimble_amd_tree.hip defines them once, over the handle's base (dispatch_handle.hpp).
-// The task-space entries are routed here, but every instantiation only forwards them to that one build (tree_model_host.hpp).
+// The task-space entries and the reverse pass of IK are routed here, but every instantiation only forwards them to that one build
+// (tree_model_host.hpp).
 // Host code only; no HIP call of its own.
 #include <cstddef>
 #include <cstdint>
@@ -83,6 +84,9 @@
   int32_t nbl_task_accel##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, double*, void*);  \
   int32_t nbl_task_accel_vjp##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, const double*,         \
                                 double*, double*, int32_t, void*, size_t, void*);                                                          \
+  size_t nbl_ik_grad_workspace_bytes##S(const void*, const nbl_kin_map*, int64_t);                                                         \
+  int32_t nbl_ik_solve_vjp##S(void*, const nbl_kin_map*, int64_t, const double*, const double*, double, double*, int32_t, int32_t*, void*, \
+                              size_t, void*);                                                                                              \
   nbl_tree_model* nbl_model_tree##S(void*);
 
 extern "C" {
@@ -144,6 +148,8 @@ struct Variant {
   int32_t (*task_accel)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, double*, void*);
   int32_t (*task_accel_vjp)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, const double*, double*, double*, int32_t,
                             void*, size_t, void*);
+  size_t (*ik_grad_workspace_bytes)(const void*, const nbl_kin_map*, int64_t);
+  int32_t (*ik_solve_vjp)(void*, const nbl_kin_map*, int64_t, const double*, const double*, double, double*, int32_t, int32_t*, void*, size_t, void*);
   nbl_tree_model* (*model_tree)(void*);
 };
 #define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
@@ -156,7 +162,7 @@ struct Variant {
    nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
    nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_contact_readout##S, nbl_contact_readout_rows##S,          \
    nbl_contact_body_wrenches##S, nbl_task_workspace_bytes##S, nbl_task_jacobian##S, nbl_task_jacobian_deriv##S, nbl_task_jacobian_vjp##S,       \
-   nbl_task_accel##S, nbl_task_accel_vjp##S, nbl_model_tree##S}
+   nbl_task_accel##S, nbl_task_accel_vjp##S, nbl_ik_grad_workspace_bytes##S, nbl_ik_solve_vjp##S, nbl_model_tree##S}
 constexpr int kNumVariants = 4;
 static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
                                                      NBL_VARIANT_TABLE(128, _c128)};
@@ -386,6 +392,13 @@ int32_t nbl_task_accel_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_
                            const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
                            size_t workspace_bytes, void* stream) {
   return NBL_TASK(m, task_accel_vjp, k, B, rows, n, state, accel, g_out, grad_state, grad_accel, accumulate, workspace, workspace_bytes, stream);
+}
+
+// ---- the reverse pass of inverse kinematics: routed like the task-space entries ----
+size_t nbl_ik_grad_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) { return NBL_GET(m, ik_grad_workspace_bytes, k, B); }
+int32_t nbl_ik_solve_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
+                         double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
+  return NBL_TASK(m, ik_solve_vjp, k, B, q, grad_q, grad_damping, grad_target, accumulate, free_count, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // nimble_amd_tree.hip — the contact-independent entry points of include/nimble_amd.h: world-space kinematics, inverse and forward dynamics,
-// mass matrix and its inverse, wrenches, contact inverse dynamics, inertia-parameter gradients, IK, centroidal quantities, sensors and
-// task-space Jacobians and accelerations.
+// mass matrix and its inverse, wrenches, contact inverse dynamics, inertia-parameter gradients, IK, centroidal quantities, sensors,
+// task-space Jacobians and accelerations and the reverse pass of IK.
 //
 // None of them depends on the contact capacity, so they are built ONCE (device namespace nbl_tree) and not once per instantiation of the
 // contact stage (abi_variants.h): every call works on the capacity-independent base of the handle, nbl_tree_model (tree_model_host.hpp),
@@ -28,6 +28,7 @@ static int fail(int code, const std::string& msg) { return ownError(code, msg.c_
 #include "sensors.hip"
 #include "taskspace.hip"
 #include "ik.hip"
+#include "ik_grad.hip"
 
 using namespace NBL_NS;
 
@@ -854,3 +855,35 @@ int32_t treeTaskAccelVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int
   return NBL_OK;
 }
 #undef TASK_GRID
+
+// ---- the reverse pass of inverse kinematics (csrc/ik_grad.hip) ----------------------------------------------------------------------------
+// Built once, here, and reached like the task-space calls: nbl_ik_grad_workspace_bytes / nbl_ik_solve_vjp of include/nimble_amd.h are thin
+// forwards in every instantiation (nimble_amd.hip) to the two functions below on the handle's base (tree_model_host.hpp declares them).
+size_t treeIkGradWorkspaceBytes(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B) {
+  return (m && k && k->capacity == m->capacity) ? ikWorkspaceBytes(m, k, B) : 0;   // the solver's layout: J, the normal matrix, three vectors
+}
+
+int32_t treeIkSolveVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
+                       double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!m) return fail(NBL_E_BADARG, "null model handle");
+  if (!k) return fail(NBL_E_BADARG, "null kinematics map");
+  if (k->capacity != m->capacity || k->n != m->n || k->nb != m->nb || k->device != m->device)
+    return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (!(grad_damping >= 0.0)) return fail(NBL_E_BADARG, "grad_damping must not be negative");
+  if (grad_damping == 0.0)
+    return fail(NBL_E_UNSUPPORTED, "grad_damping = 0 (a pseudo-inverse of a possibly singular Jacobian) is outside the device path");
+  if (B == 0) return NBL_OK;
+  if (!q || !grad_q || !grad_target || !workspace) return fail(NBL_E_BADARG, "null argument");
+  if ((B + IK_GRAD_BLOCK - 1) / IK_GRAD_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  const size_t need = ikWorkspaceBytes(m, k, B);
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, "IK gradient workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, nbl_ik_grad_workspace_bytes() = " + std::to_string(need));
+  DeviceGuard guard(m->device);
+  hipLaunchKernelGGL(k_ik_solve_vjp, dim3((unsigned)((B + IK_GRAD_BLOCK - 1) / IK_GRAD_BLOCK)), dim3(IK_GRAD_BLOCK), 0, (hipStream_t)stream,
+                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
+                     m->nb, m->n, k->P, B, q, grad_q, grad_damping, grad_target, accumulate ? 1 : 0, free_count, (double*)workspace);
+  HIP_TRY(hipGetLastError());
+  return NBL_OK;
+}

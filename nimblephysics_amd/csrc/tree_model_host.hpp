@@ -92,3 +92,9 @@ int32_t treeTaskAccel(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_
 int32_t treeTaskAccelVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
                          const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+// The reverse pass of inverse kinematics (csrc/ik_grad.hip) goes the same way: defined once in nimble_amd_tree.hip, forwarded to by
+// nbl_ik_grad_workspace_bytes / nbl_ik_solve_vjp of every instantiation.
+size_t treeIkGradWorkspaceBytes(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B);
+int32_t treeIkSolveVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
+                       double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream);

@@ -14,8 +14,9 @@ Differences from the reference, all forced by batching or by this library's mode
     returns - gives `[B, T+1, P]`); CPU float64 tensors come back as CPU tensors, device tensors stay on the device;
   * neither function changes the World's state (the reference's layers call world.setState).
 The setters (IKMapping.cpp:86-135): `setPositions` runs the batched inverse-kinematics solve of csrc/ik.hip (`solve_ik`: the reference's
-math::solveIK with one restart, one world per lane, no autograd - the reference has none), `setVelocities` applies the pseudo-inverse of
-the velocity Jacobian, `setControlForces` its transpose.
+math::solveIK with one restart, one world per lane; no autograd, as in the reference, unless `differentiable=True` asks for the gradient
+to the targets of csrc/ik_grad.hip), `setVelocities` applies the pseudo-inverse of the velocity Jacobian, `setControlForces` its
+transpose.
 What stays out: COM entries (no public constructor in the reference), IdentityMapping, MappedBackpropSnapshot and world.addMapping.
 """
 from __future__ import annotations
@@ -345,14 +346,64 @@ def _solve_ik_soa(world, mapping: "IKMapping", t_soa: torch.Tensor, init_soa, co
     return q, loss, steps
 
 
-def solve_ik(world, map: "IKMapping", targets: torch.Tensor, init: Optional[torch.Tensor] = None, config: Optional[IKConfig] = None):
-    """Batched inverse kinematics: joint positions whose mapped positions (`map_to_pos`) meet `targets`, by the reference's
-    math::solveIK with one restart (20 steps of refineIK, then config.max_step_count steps; IKSolver.cpp:195-493), one world per lane of
-    csrc/ik.hip.  targets [B, P] or [P]; init [B, n] / [n] (None: zeros, as IKMapping::setPositions starts); config None: IKConfig()
-    (the reference's defaults, 100 steps).  Returns (q [B, n], loss [B] = |rows(q) - target|^2 at q, steps [B] int32 = evaluations
-    used); [P] gives q [n] and 0-d loss / steps.  CPU tensors come back as CPU tensors.  The World's state is left untouched; a World in
-    deferred-join mode is joined first.  No autograd: the reference has none either.  On a World with immobile skeletons q is over the
-    mobile coordinates (init may come in either layout)."""
+def _check_grad_damping(grad_damping, what: str) -> float:
+    mu = float(grad_damping)
+    if not mu >= 0.0:
+        raise ValueError(f"{what}: grad_damping must not be negative (got {grad_damping})")
+    if mu == 0.0:                                      # NBL_E_UNSUPPORTED of nbl_ik_solve_vjp, said before anything is solved
+        raise NimbleAmdError(f"{what}: grad_damping = 0 (a pseudo-inverse of a possibly singular Jacobian) is outside the device path")
+    return mu
+
+
+def _solve_ik_vjp_soa(world, mapping: "IKMapping", q_soa: torch.Tensor, g_soa: torch.Tensor, grad_damping: float):
+    """q, grad_q [n][B] -> (grad_target [P][B], free_count [B] int32) on the World's device; cut into launches like _solve_ik_soa (a
+    world's result does not depend on the cut)"""
+    _join_if_deferred(world)
+    P, B, n = mapping.getPosDim(), q_soa.shape[1], world.n
+    if P == 0:
+        raise ValueError("solve_ik_vjp: the mapping has no entries")
+    gt = torch.empty((P, B), dtype=torch.float64, device=world.device)
+    free = torch.empty((B,), dtype=torch.int32, device=world.device)
+    if B == 0:
+        return gt, free
+    km = mapping._device_map(world)
+    L = world._L
+    per = L.nbl_ik_grad_workspace_bytes(world._h, km, 1)
+    chunk = max(64, (IK_WORKSPACE_BYTES // max(per, 1)) // 64 * 64)
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        whole = b0 == 0 and b1 == B
+        qc = q_soa if whole else q_soa[:, b0:b1].contiguous()
+        gc = g_soa if whole else g_soa[:, b0:b1].contiguous()
+        oc = gt if whole else torch.empty((P, b1 - b0), dtype=torch.float64, device=world.device)
+        need = L.nbl_ik_grad_workspace_bytes(world._h, km, b1 - b0)
+        ws = getattr(world, "_ik_ws", None)
+        if ws is None or ws.numel() < need or ws.device != world.device:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=world.device)
+            world._ik_ws = ws
+        check(L.nbl_ik_solve_vjp(world._h, km, b1 - b0, _ptr(qc), _ptr(gc), grad_damping, _ptr(oc), 0, _ptr(free[b0:b1]), _ptr(ws),
+                                 ws.numel(), world._stream()), "nbl_ik_solve_vjp")
+        if not whole:
+            gt[:, b0:b1] = oc
+    return gt, free
+
+
+def _coords_soa(world, x: torch.Tensor, B: Optional[int], what: str, name: str) -> torch.Tensor:
+    """[B, n] / [n] joint coordinates (or the reference's layout on a World with immobile skeletons) -> [n][B] on the World's device"""
+    given = tuple(x.shape)
+    x = x.detach()
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    lay = world.ref_layout
+    if lay is not None and x.shape[-1] == lay.n_ref:
+        x = x.index_select(-1, lay._idx(x.device, "mobile"))
+    if x.dim() != 2 or x.shape[1] != world.n or (B is not None and x.shape[0] != B):
+        raise ValueError(f"{what}: {name} has shape {given}; expected [{'B' if B is None else B}, {world.n}]")
+    return world.to_soa(world._prep(x, world.n, "ik_" + name))
+
+
+def _solve_ik_detached(world, map: "IKMapping", targets: torch.Tensor, init, config):
+    """solve_ik without autograd -> (q, loss, steps as solve_ik returns them, q [n][B] on the World's device)"""
     _join_if_deferred(world)
     one = targets.dim() == 1
     t_soa = _targets_soa(world, map, targets, None, "solve_ik")
@@ -375,7 +426,70 @@ def solve_ik(world, map: "IKMapping", targets: torch.Tensor, init: Optional[torc
         steps = steps.cpu()
     else:
         q, loss, steps = q.to(targets.device), loss.to(targets.device), steps.to(targets.device)
-    return (q[0], loss[0], steps[0]) if one else (q, loss, steps)
+    return ((q[0], loss[0], steps[0]) if one else (q, loss, steps)) + (q_soa,)
+
+
+class SolveIKLayer(torch.autograd.Function):
+    """solve_ik(..., differentiable=True): forward = the solve; backward = nbl_ik_solve_vjp at the returned positions (the Gauss-Newton
+    sensitivity on the free coordinates, csrc/ik_grad.hip) into `targets`.  `init` gets None; loss and steps carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, world, mapping, targets, init, config, grad_damping):
+        q, loss, steps, q_soa = _solve_ik_detached(world, mapping, targets, init, config)
+        ctx.world, ctx.mapping, ctx.q_soa, ctx.mu = world, mapping, q_soa, grad_damping
+        ctx.one, ctx.in_device = targets.dim() == 1, targets.device
+        ctx.mark_non_differentiable(loss, steps)
+        return q, loss, steps
+
+    @staticmethod
+    def backward(ctx, grad_q, _grad_loss, _grad_steps):
+        world = ctx.world
+        g = grad_q.detach().to(device=world.device, dtype=torch.float64).reshape(-1, world.n)
+        gt_soa, _ = _solve_ik_vjp_soa(world, ctx.mapping, ctx.q_soa, world.to_soa(g), ctx.mu)
+        gt = world.from_soa(gt_soa)
+        gt = world._to_host(gt) if ctx.in_device.type == "cpu" else gt.to(ctx.in_device)
+        return None, None, (gt[0] if ctx.one else gt), None, None, None
+
+
+def solve_ik(world, map: "IKMapping", targets: torch.Tensor, init: Optional[torch.Tensor] = None, config: Optional[IKConfig] = None,
+             differentiable: bool = False, grad_damping: float = 1e-9):
+    """Batched inverse kinematics: joint positions whose mapped positions (`map_to_pos`) meet `targets`, by the reference's
+    math::solveIK with one restart (20 steps of refineIK, then config.max_step_count steps; IKSolver.cpp:195-493), one world per lane of
+    csrc/ik.hip.  targets [B, P] or [P]; init [B, n] / [n] (None: zeros, as IKMapping::setPositions starts); config None: IKConfig()
+    (the reference's defaults, 100 steps).  Returns (q [B, n], loss [B] = |rows(q) - target|^2 at q, steps [B] int32 = evaluations
+    used); [P] gives q [n] and 0-d loss / steps.  CPU tensors come back as CPU tensors.  The World's state is left untouched; a World in
+    deferred-join mode is joined first.  On a World with immobile skeletons q is over the mobile coordinates (init may come in either
+    layout).
+
+    differentiable=False (the default): no autograd, whatever `targets` requires - the reference has none either.
+    differentiable=True: q carries the gradient to `targets` that csrc/ik_grad.hip computes (`solve_ik_vjp`): with J the position
+    Jacobian at q and F the coordinates NOT left exactly on a finite limit, grad_targets = J_F (J_F^T J_F + mu I)^-1 (grad_q)_F with
+    mu = grad_damping > 0 (a Tikhonov term of the gradient alone, not config.least_squares_damping; 0 raises).  Two limits: the
+    second-order term sum_k (rows(q) - target)_k grad^2 rows_k is left out, so this is the derivative of the solve where the target is met
+    and its Gauss-Newton approximation elsewhere; and `init` gets no gradient (None).  loss and steps stay detached."""
+    if not differentiable:
+        return _solve_ik_detached(world, map, targets, init, config)[:3]
+    return SolveIKLayer.apply(world, map, targets, init, config, _check_grad_damping(grad_damping, "solve_ik"))
+
+
+def solve_ik_vjp(world, map: "IKMapping", q: torch.Tensor, grad_q: torch.Tensor, grad_damping: float = 1e-9):
+    """The backward pass of solve_ik(differentiable=True) as a function, without autograd: q [B, n] / [n] as solve_ik returned it, grad_q
+    alike -> (grad_targets [B, P] / [P], free_count [B] int32 / 0-d: the coordinates of each world not left exactly on a finite limit).
+    CPU tensors come back as CPU tensors; a World in deferred-join mode is joined first."""
+    mu = _check_grad_damping(grad_damping, "solve_ik_vjp")
+    _join_if_deferred(world)
+    one = q.dim() == 1
+    if grad_q.dim() != q.dim():
+        raise ValueError(f"solve_ik_vjp: q has shape {tuple(q.shape)} and grad_q {tuple(grad_q.shape)}")
+    q_soa = _coords_soa(world, q, None, "solve_ik_vjp", "q")
+    g_soa = _coords_soa(world, grad_q, q_soa.shape[1], "solve_ik_vjp", "grad_q")
+    gt_soa, free = _solve_ik_vjp_soa(world, map, q_soa, g_soa, mu)
+    gt = world.from_soa(gt_soa)
+    if q.device.type == "cpu":
+        gt, free = world._to_host(gt), free.cpu()
+    else:
+        gt, free = gt.to(q.device), free.to(q.device)
+    return (gt[0], free[0]) if one else (gt, free)
 
 
 def _join_if_deferred(world):
