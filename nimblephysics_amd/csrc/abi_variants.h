@@ -10,9 +10,10 @@
  * that all fit in one shared library: model creation, the step, the rollouts, inertia patches, slices, timing, the self-tests and the
  * contact read-out - whatever reads LCP rows, collider budgets or the saved record.  nimble_amd_dispatch.cpp exports those names of
  * include/nimble_amd.h and hands every model to the instantiation that fits it (nbl_model_create).
- * The CONTACT-INDEPENDENT calls - kinematics maps, inverse and forward dynamics, mass matrix, wrenches, inertia-parameter gradients, IK,
- * body sets and centroidal quantities, sensors - are not renamed and not dispatched: nimble_amd_tree.hip defines them once, under their
- * public names, over the capacity-independent base of a handle (tree_model_host.hpp; nbl_model_tree below hands it out).
+ * The 43 CONTACT-INDEPENDENT calls - kinematics maps, inverse and forward dynamics, mass matrix, wrenches, inertia-parameter gradients, IK and
+ * its reverse pass, body sets and centroidal quantities, sensors, task-space Jacobians and accelerations - are not renamed and not
+ * dispatched: nimble_amd_tree.hip defines them once, under their public names, over the capacity-independent base of a handle
+ * (tree_model_host.hpp; nbl_model_tree below hands it out).
  * Without NBL_VARIANT_SUFFIX nothing is renamed: nimble_amd.hip alone, which then includes nimble_amd_tree.hip, is the whole library
  * in its 8-contact form (the developer builds of tools/ compile it that way).
  */
@@ -79,16 +80,6 @@
 #define nbl_contact_readout NBL_V(nbl_contact_readout)
 #define nbl_contact_readout_rows NBL_V(nbl_contact_readout_rows)
 #define nbl_contact_body_wrenches NBL_V(nbl_contact_body_wrenches)
-/* the task-space entries: per instantiation only as thin forwards; their kernels are built once (nimble_amd_tree.hip, tree_model_host.hpp) */
-#define nbl_task_workspace_bytes NBL_V(nbl_task_workspace_bytes)
-#define nbl_task_jacobian NBL_V(nbl_task_jacobian)
-#define nbl_task_jacobian_deriv NBL_V(nbl_task_jacobian_deriv)
-#define nbl_task_jacobian_vjp NBL_V(nbl_task_jacobian_vjp)
-#define nbl_task_accel NBL_V(nbl_task_accel)
-#define nbl_task_accel_vjp NBL_V(nbl_task_accel_vjp)
-/* the reverse pass of IK: thin forwards like the task-space entries (kernel built once: csrc/ik_grad.hip) */
-#define nbl_ik_grad_workspace_bytes NBL_V(nbl_ik_grad_workspace_bytes)
-#define nbl_ik_solve_vjp NBL_V(nbl_ik_solve_vjp)
 #define nbl_model_tree NBL_V(nbl_model_tree)  /* (not in the ABI: the handle's base for nimble_amd_tree.hip, tree_model_host.hpp) */
 #elif !defined(NBL_DISPATCHER)
 /* the stand-alone 8-contact build has nobody to hand the model on to */

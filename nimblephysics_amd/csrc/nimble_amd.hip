@@ -1761,41 +1761,10 @@ int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, in
   return NBL_OK;
 }
 
-// ---- task-space Jacobians and accelerations: the kernels and the checks are built once (nimble_amd_tree.hip, csrc/taskspace.hip); every
-// instantiation forwards its handle's base to them ----
-size_t nbl_task_workspace_bytes(const nbl_model* m, int64_t B) { return treeTaskWorkspaceBytes(m, B); }
-int32_t nbl_task_jacobian(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream) {
-  return treeTaskJacobian(m, k, B, rows, n, state, J, stream);
-}
-int32_t nbl_task_jacobian_deriv(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
-                                void* stream) {
-  return treeTaskJacobianDeriv(m, k, B, rows, n, state, Jdot, stream);
-}
-int32_t nbl_task_jacobian_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
-                              double* grad_q, int32_t accumulate, void* stream) {
-  return treeTaskJacobianVjp(m, k, B, rows, n, state, G, grad_q, accumulate, stream);
-}
-int32_t nbl_task_accel(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
-                       double* bias, double* xdd, void* stream) {
-  return treeTaskAccel(m, k, B, rows, n, state, accel, bias, xdd, stream);
-}
-int32_t nbl_task_accel_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
-                           const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  return treeTaskAccelVjp(m, k, B, rows, n, state, accel, g_out, grad_state, grad_accel, accumulate, workspace, workspace_bytes, stream);
-}
-
-// ---- the reverse pass of inverse kinematics (csrc/ik_grad.hip): built once like the task-space kernels, forwarded to like them ----
-size_t nbl_ik_grad_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) { return treeIkGradWorkspaceBytes(m, k, B); }
-int32_t nbl_ik_solve_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
-                         double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
-  return treeIkSolveVjp(m, k, B, q, grad_q, grad_damping, grad_target, accumulate, free_count, workspace, workspace_bytes, stream);
-}
-
 }  // extern "C"
 
-// The contact-independent calls (kinematics, dynamics, IK, centroidal quantities, sensors) live in nimble_amd_tree.hip and work on the
-// capacity-independent base of a handle.
+// The contact-independent calls (kinematics, dynamics, IK, centroidal quantities, sensors, task-space quantities) live in
+// nimble_amd_tree.hip and work on the capacity-independent base of a handle.
 #ifdef NBL_VARIANT_SUFFIX
 // one unit, built once, serves every instantiation: the dispatcher fetches the base once per model through this accessor
 extern "C" nbl_tree_model* nbl_model_tree(nbl_model* m) { return m; }

@@ -3,9 +3,7 @@
 // BASELINE config), to the 48-row build (up to 16 contacts, 32 colliders, 64 pairs per world) or to the GENERAL build (up to 64
 // contacts = 192 LCP rows, 64 colliders, 512 pairs: rows looped over instead of mapped to lanes - there so that no legal world
 // gets a truncated answer; 2 M world-steps/s on eight-contact worlds since round 6; a fourth instantiation is the same code with 384 rows); every later call that exists per capacity goes to the build that owns the handle.
-// The contact-independent calls are not dispatched: nimble_amd_tree.hip defines them once, over the handle's base (dispatch_handle.hpp).
-// The task-space entries and the reverse pass of IK are routed here, but every instantiation only forwards them to that one build
-// (tree_model_host.hpp).
+// The 43 contact-independent calls are not dispatched: nimble_amd_tree.hip defines them once, over the handle's base (dispatch_handle.hpp).
 // Host code only; no HIP call of its own.
 #include <cstddef>
 #include <cstdint>
@@ -16,156 +14,90 @@
 #define NBL_DISPATCHER
 #include "abi_variants.h"
 
-// the same signatures as include/nimble_amd.h with the handle as void* (C linkage: no type in the symbol)
-#define NBL_DECLARE_VARIANT(S)                                                                                                              \
-  const char* nbl_last_error##S(void);                                                                                                     \
-  int32_t nbl_version##S(void);                                                                                                            \
-  int32_t nbl_device_count##S(void);                                                                                                       \
-  int32_t nbl_model_create##S(const nbl_model_desc*, int32_t, void**);                                                                     \
-  void nbl_model_destroy##S(void*);                                                                                                        \
-  int32_t nbl_model_num_dofs##S(const void*);                                                                                              \
-  int32_t nbl_model_num_action##S(const void*);                                                                                            \
-  int32_t nbl_model_lcp_rows##S(const void*);                                                                                              \
-  int32_t nbl_model_max_contacts##S(const void*);                                                                                          \
-  size_t nbl_workspace_bytes##S(const void*, int64_t);                                                                                     \
-  size_t nbl_saved_bytes##S(const void*, int64_t);                                                                                         \
-  int32_t nbl_step_forward##S(void*, int64_t, const double*, const double*, const double*, double*, double*, void*, uint32_t*, void*,      \
-                              size_t, void*);                                                                                              \
-  int32_t nbl_step_backward##S(void*, int64_t, const void*, const double*, double*, double*, void*, size_t, void*);                        \
-  int32_t nbl_set_body_inertia##S(void*, int32_t, double, const double*, const double*);                                                   \
-  int32_t nbl_set_body_inertias##S(void*, int32_t, const int32_t*, const double*, const double*, const double*, void*);                    \
-  int32_t nbl_set_inertia_params##S(void*, int32_t, const int32_t*, const double*);                                                        \
-  int32_t nbl_set_inertia_params_on##S(void*, int32_t, const int32_t*, const double*, void*);                                              \
-  int32_t nbl_num_inertia_params##S(const void*);                                                                                          \
-  int32_t nbl_backward_inertia##S(void*, int64_t, const void*, double*, int32_t, void*, size_t, void*);                                    \
-  size_t nbl_rollout_workspace_bytes##S(const void*, int64_t);                                                                             \
-  int32_t nbl_rollout_forward##S(void*, int64_t, int32_t, const double*, const double*, int64_t, double*, void*, uint32_t*, int32_t,       \
-                                 void*, size_t, void*);                                                                                    \
-  int32_t nbl_rollout_backward##S(void*, int64_t, int32_t, const void*, const double*, double*, double*, void*, size_t, void*);            \
-  int32_t nbl_rollout_backward_inertia##S(void*, int64_t, int32_t, const void*, const double*, double*, double*, double*, void*, size_t,   \
-                                          void*);                                                                                          \
-  size_t nbl_rollout_checkpoint_bytes##S(const void*, int64_t, int32_t, int32_t);                                                          \
-  int32_t nbl_rollout_forward_checkpointed##S(void*, int64_t, int32_t, int32_t, const double*, const double*, int64_t, double*, void*,     \
-                                              void*, uint32_t*, int32_t, void*, size_t, void*);                                            \
-  int32_t nbl_rollout_backward_checkpointed##S(void*, int64_t, int32_t, int32_t, double*, const double*, int64_t, void*, const void*,      \
-                                               int32_t, const double*, double*, double*, double*, void*, size_t, void*);                   \
-  int32_t nbl_selftest_lcp_dantzig_timed##S(int32_t, int32_t, const double*, const double*, const double*, const double*, const int32_t*,  \
-                                            double*, int32_t*, int32_t, double*);                                                          \
-  int32_t nbl_selftest_pinv_rows##S(int32_t, int32_t, const double*, const int32_t*, int32_t, double*, int32_t*, int32_t, double*);        \
-  int32_t nbl_selftest_stage0_rows##S(int32_t, int32_t, const double*, const double*, const double*, const uint64_t*, const uint64_t*,     \
-                                      const uint64_t*, const double*, const int32_t*, const double*, double*, double*, int32_t*, double*,  \
-                                      int32_t*, double*);                                                                                  \
-  int32_t nbl_selftest_lcp_cascade##S(int32_t, int32_t, const double*, const double*, const double*, int32_t, const double*, const uint8_t*, double,   \
-                                      double*, int32_t*, uint32_t*, double*);                                                              \
-  int32_t nbl_selftest_lcp_cascade_rows##S(int32_t, int32_t, const double*, const double*, const double*, const double*, const uint8_t*,   \
-                                           int32_t, const double*, const uint8_t*, double, double*, int32_t*, uint32_t*, double*);         \
-  int32_t nbl_transpose_to_soa##S(const double*, double*, int64_t, int32_t, void*);                                                        \
-  int32_t nbl_transpose_from_soa##S(const double*, double*, int64_t, int32_t, void*);                                                      \
-  int32_t nbl_set_launch_lanes##S(void*, int32_t, int32_t);                                                                                \
-  int32_t nbl_set_slices##S(void*, int32_t);                                                                                               \
-  int32_t nbl_slices_for##S(const void*, int64_t);                                                                                         \
-  int32_t nbl_set_deferred_join##S(void*, int32_t);                                                                                        \
-  int32_t nbl_slice_stream##S(void*, int64_t, int32_t, void**, int64_t*, int64_t*);                                                        \
-  int32_t nbl_join_slices##S(void*, void*);                                                                                                \
-  int32_t nbl_fork_slices##S(void*, void*);                                                                                                \
-  int32_t nbl_set_timing##S(void*, int32_t);                                                                                               \
-  int32_t nbl_get_timing##S(void*, double*, int64_t*, double*, int64_t*);                                                                  \
-  int32_t nbl_kernel_count##S(void);                                                                                                       \
-  const char* nbl_kernel_name##S(int32_t);                                                                                                 \
-  int32_t nbl_kernel_timing##S(void*, int32_t, double*, int64_t*);                                                                         \
-  int32_t nbl_contact_readout##S(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);                              \
-  int32_t nbl_contact_readout_rows##S(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);                                   \
-  int32_t nbl_contact_body_wrenches##S(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);                              \
-  size_t nbl_task_workspace_bytes##S(const void*, int64_t);                                                                                \
-  int32_t nbl_task_jacobian##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);                       \
-  int32_t nbl_task_jacobian_deriv##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);                 \
-  int32_t nbl_task_jacobian_vjp##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, int32_t,   \
-                                   void*);                                                                                                 \
-  int32_t nbl_task_accel##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, double*, void*);  \
-  int32_t nbl_task_accel_vjp##S(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, const double*,         \
-                                double*, double*, int32_t, void*, size_t, void*);                                                          \
-  size_t nbl_ik_grad_workspace_bytes##S(const void*, const nbl_kin_map*, int64_t);                                                         \
-  int32_t nbl_ik_solve_vjp##S(void*, const nbl_kin_map*, int64_t, const double*, const double*, double, double*, int32_t, int32_t*, void*, \
-                              size_t, void*);                                                                                              \
-  nbl_tree_model* nbl_model_tree##S(void*);
+// The entry points every instantiation defines under its suffix and a model's calls reach through its owner's table: X(S, return type,
+// name without nbl_, parameters) - the signatures of include/nimble_amd.h with the handle as void* (C linkage: no type in the symbol).
+// The prototypes, the members of Variant and the rows of kVariants are all expanded from this one list.
+#define NBL_PER_CAPACITY(X, S)                                                                                                              \
+  X(S, const char*, last_error, (void))                                                                                                    \
+  X(S, int32_t, model_create, (const nbl_model_desc*, int32_t, void**))                                                                    \
+  X(S, void, model_destroy, (void*))                                                                                                       \
+  X(S, int32_t, model_num_dofs, (const void*))                                                                                             \
+  X(S, int32_t, model_num_action, (const void*))                                                                                           \
+  X(S, int32_t, model_lcp_rows, (const void*))                                                                                             \
+  X(S, int32_t, model_max_contacts, (const void*))                                                                                         \
+  X(S, size_t, workspace_bytes, (const void*, int64_t))                                                                                    \
+  X(S, size_t, saved_bytes, (const void*, int64_t))                                                                                        \
+  X(S, int32_t, step_forward, (void*, int64_t, const double*, const double*, const double*, double*, double*, void*, uint32_t*, void*,     \
+                               size_t, void*))                                                                                             \
+  X(S, int32_t, step_backward, (void*, int64_t, const void*, const double*, double*, double*, void*, size_t, void*))                       \
+  X(S, int32_t, set_body_inertia, (void*, int32_t, double, const double*, const double*))                                                  \
+  X(S, int32_t, set_body_inertias, (void*, int32_t, const int32_t*, const double*, const double*, const double*, void*))                   \
+  X(S, int32_t, set_inertia_params, (void*, int32_t, const int32_t*, const double*))                                                       \
+  X(S, int32_t, set_inertia_params_on, (void*, int32_t, const int32_t*, const double*, void*))                                             \
+  X(S, int32_t, num_inertia_params, (const void*))                                                                                         \
+  X(S, int32_t, backward_inertia, (void*, int64_t, const void*, double*, int32_t, void*, size_t, void*))                                   \
+  X(S, size_t, rollout_workspace_bytes, (const void*, int64_t))                                                                            \
+  X(S, int32_t, rollout_forward, (void*, int64_t, int32_t, const double*, const double*, int64_t, double*, void*, uint32_t*, int32_t,      \
+                                  void*, size_t, void*))                                                                                   \
+  X(S, int32_t, rollout_backward, (void*, int64_t, int32_t, const void*, const double*, double*, double*, void*, size_t, void*))           \
+  X(S, int32_t, rollout_backward_inertia, (void*, int64_t, int32_t, const void*, const double*, double*, double*, double*, void*, size_t,  \
+                                           void*))                                                                                         \
+  X(S, size_t, rollout_checkpoint_bytes, (const void*, int64_t, int32_t, int32_t))                                                         \
+  X(S, int32_t, rollout_forward_checkpointed, (void*, int64_t, int32_t, int32_t, const double*, const double*, int64_t, double*, void*,    \
+                                               void*, uint32_t*, int32_t, void*, size_t, void*))                                           \
+  X(S, int32_t, rollout_backward_checkpointed, (void*, int64_t, int32_t, int32_t, double*, const double*, int64_t, void*, const void*,     \
+                                                int32_t, const double*, double*, double*, double*, void*, size_t, void*))                  \
+  X(S, int32_t, selftest_lcp_dantzig_timed, (int32_t, int32_t, const double*, const double*, const double*, const double*, const int32_t*, \
+                                             double*, int32_t*, int32_t, double*))                                                         \
+  X(S, int32_t, selftest_pinv_rows, (int32_t, int32_t, const double*, const int32_t*, int32_t, double*, int32_t*, int32_t, double*))       \
+  X(S, int32_t, set_launch_lanes, (void*, int32_t, int32_t))                                                                               \
+  X(S, int32_t, set_slices, (void*, int32_t))                                                                                              \
+  X(S, int32_t, slices_for, (const void*, int64_t))                                                                                        \
+  X(S, int32_t, set_deferred_join, (void*, int32_t))                                                                                       \
+  X(S, int32_t, slice_stream, (void*, int64_t, int32_t, void**, int64_t*, int64_t*))                                                       \
+  X(S, int32_t, join_slices, (void*, void*))                                                                                               \
+  X(S, int32_t, fork_slices, (void*, void*))                                                                                               \
+  X(S, int32_t, set_timing, (void*, int32_t))                                                                                              \
+  X(S, int32_t, get_timing, (void*, double*, int64_t*, double*, int64_t*))                                                                 \
+  X(S, int32_t, kernel_timing, (void*, int32_t, double*, int64_t*))                                                                        \
+  X(S, int32_t, contact_readout, (void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*))                              \
+  X(S, int32_t, contact_readout_rows, (void*, int64_t, const void*, int32_t*, double*, int32_t*, void*))                                   \
+  X(S, int32_t, contact_body_wrenches, (void*, int64_t, const void*, int32_t, const int32_t*, double*, void*))                             \
+  X(S, nbl_tree_model*, model_tree, (void*))
+#define NBL_PROTOTYPE(S, ret, name, params) ret nbl_##name##S params;
+#define NBL_MEMBER(S, ret, name, params) ret (*name) params;
+#define NBL_ENTRY(S, ret, name, params) nbl_##name##S,
 
 extern "C" {
-NBL_DECLARE_VARIANT(_c8)
-NBL_DECLARE_VARIANT(_c16)
-NBL_DECLARE_VARIANT(_c64)
-NBL_DECLARE_VARIANT(_c128)
+NBL_PER_CAPACITY(NBL_PROTOTYPE, _c8)
+NBL_PER_CAPACITY(NBL_PROTOTYPE, _c16)
+NBL_PER_CAPACITY(NBL_PROTOTYPE, _c64)
+NBL_PER_CAPACITY(NBL_PROTOTYPE, _c128)
+// called by their suffix below, not through a table
+int32_t nbl_version_c8(void);
+int32_t nbl_device_count_c8(void);
+int32_t nbl_kernel_count_c8(void);
+const char* nbl_kernel_name_c8(int32_t);
+int32_t nbl_transpose_to_soa_c8(const double*, double*, int64_t, int32_t, void*);
+int32_t nbl_transpose_from_soa_c8(const double*, double*, int64_t, int32_t, void*);
+int32_t nbl_selftest_lcp_cascade_c64(int32_t, int32_t, const double*, const double*, const double*, int32_t, const double*, const uint8_t*, double,
+                                     double*, int32_t*, uint32_t*, double*);
+int32_t nbl_selftest_lcp_cascade_rows_c64(int32_t, int32_t, const double*, const double*, const double*, const double*, const uint8_t*, int32_t,
+                                          const double*, const uint8_t*, double, double*, int32_t*, uint32_t*, double*);
+int32_t nbl_selftest_stage0_rows_c8(int32_t, int32_t, const double*, const double*, const double*, const uint64_t*, const uint64_t*, const uint64_t*,
+                                    const double*, const int32_t*, const double*, double*, double*, int32_t*, double*, int32_t*, double*);
+int32_t nbl_selftest_stage0_rows_c16(int32_t, int32_t, const double*, const double*, const double*, const uint64_t*, const uint64_t*, const uint64_t*,
+                                     const double*, const int32_t*, const double*, double*, double*, int32_t*, double*, int32_t*, double*);
 }
 
 // one table of entry points per instantiation
 struct Variant {
-  int id;   // 8, 16 or 64: the contact slots per world of the instantiation
-  const char* (*last_error)(void);
-  int32_t (*model_create)(const nbl_model_desc*, int32_t, void**);
-  void (*model_destroy)(void*);
-  int32_t (*model_num_dofs)(const void*);
-  int32_t (*model_num_action)(const void*);
-  int32_t (*model_lcp_rows)(const void*);
-  int32_t (*model_max_contacts)(const void*);
-  size_t (*workspace_bytes)(const void*, int64_t);
-  size_t (*saved_bytes)(const void*, int64_t);
-  int32_t (*step_forward)(void*, int64_t, const double*, const double*, const double*, double*, double*, void*, uint32_t*, void*, size_t, void*);
-  int32_t (*step_backward)(void*, int64_t, const void*, const double*, double*, double*, void*, size_t, void*);
-  int32_t (*set_body_inertia)(void*, int32_t, double, const double*, const double*);
-  int32_t (*set_body_inertias)(void*, int32_t, const int32_t*, const double*, const double*, const double*, void*);
-  int32_t (*set_inertia_params)(void*, int32_t, const int32_t*, const double*);
-  int32_t (*set_inertia_params_on)(void*, int32_t, const int32_t*, const double*, void*);
-  int32_t (*num_inertia_params)(const void*);
-  int32_t (*backward_inertia)(void*, int64_t, const void*, double*, int32_t, void*, size_t, void*);
-  size_t (*rollout_workspace_bytes)(const void*, int64_t);
-  int32_t (*rollout_forward)(void*, int64_t, int32_t, const double*, const double*, int64_t, double*, void*, uint32_t*, int32_t, void*, size_t, void*);
-  int32_t (*rollout_backward)(void*, int64_t, int32_t, const void*, const double*, double*, double*, void*, size_t, void*);
-  int32_t (*rollout_backward_inertia)(void*, int64_t, int32_t, const void*, const double*, double*, double*, double*, void*, size_t, void*);
-  size_t (*rollout_checkpoint_bytes)(const void*, int64_t, int32_t, int32_t);
-  int32_t (*rollout_forward_checkpointed)(void*, int64_t, int32_t, int32_t, const double*, const double*, int64_t, double*, void*, void*, uint32_t*, int32_t,
-                                          void*, size_t, void*);
-  int32_t (*rollout_backward_checkpointed)(void*, int64_t, int32_t, int32_t, double*, const double*, int64_t, void*, const void*, int32_t, const double*,
-                                           double*, double*, double*, void*, size_t, void*);
-  int32_t (*selftest_lcp_dantzig_timed)(int32_t, int32_t, const double*, const double*, const double*, const double*, const int32_t*, double*, int32_t*,
-                                        int32_t, double*);
-  int32_t (*selftest_pinv_rows)(int32_t, int32_t, const double*, const int32_t*, int32_t, double*, int32_t*, int32_t, double*);
-  int32_t (*set_launch_lanes)(void*, int32_t, int32_t);
-  int32_t (*set_slices)(void*, int32_t);
-  int32_t (*slices_for)(const void*, int64_t);
-  int32_t (*set_deferred_join)(void*, int32_t);
-  int32_t (*slice_stream)(void*, int64_t, int32_t, void**, int64_t*, int64_t*);
-  int32_t (*join_slices)(void*, void*);
-  int32_t (*fork_slices)(void*, void*);
-  int32_t (*set_timing)(void*, int32_t);
-  int32_t (*get_timing)(void*, double*, int64_t*, double*, int64_t*);
-  int32_t (*kernel_timing)(void*, int32_t, double*, int64_t*);
-  int32_t (*contact_readout)(void*, int64_t, const void*, int32_t*, int32_t*, int32_t*, double*, void*);
-  int32_t (*contact_readout_rows)(void*, int64_t, const void*, int32_t*, double*, int32_t*, void*);
-  int32_t (*contact_body_wrenches)(void*, int64_t, const void*, int32_t, const int32_t*, double*, void*);
-  size_t (*task_workspace_bytes)(const void*, int64_t);
-  int32_t (*task_jacobian)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);
-  int32_t (*task_jacobian_deriv)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, double*, void*);
-  int32_t (*task_jacobian_vjp)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, int32_t, void*);
-  int32_t (*task_accel)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, double*, double*, void*);
-  int32_t (*task_accel_vjp)(void*, const nbl_kin_map*, int64_t, int32_t, int32_t, const double*, const double*, const double*, double*, double*, int32_t,
-                            void*, size_t, void*);
-  size_t (*ik_grad_workspace_bytes)(const void*, const nbl_kin_map*, int64_t);
-  int32_t (*ik_solve_vjp)(void*, const nbl_kin_map*, int64_t, const double*, const double*, double, double*, int32_t, int32_t*, void*, size_t, void*);
-  nbl_tree_model* (*model_tree)(void*);
+  int id;   // 8, 16, 64 or 128: the contact slots per world of the instantiation
+  NBL_PER_CAPACITY(NBL_MEMBER, )
 };
-#define NBL_VARIANT_TABLE(ID, S)                                                                                                              \
-  {ID, nbl_last_error##S, nbl_model_create##S, nbl_model_destroy##S, nbl_model_num_dofs##S, nbl_model_num_action##S, nbl_model_lcp_rows##S,    \
-   nbl_model_max_contacts##S, nbl_workspace_bytes##S, nbl_saved_bytes##S, nbl_step_forward##S, nbl_step_backward##S, nbl_set_body_inertia##S, \
-   nbl_set_body_inertias##S, nbl_set_inertia_params##S, nbl_set_inertia_params_on##S, nbl_num_inertia_params##S, nbl_backward_inertia##S,     \
-   nbl_rollout_workspace_bytes##S, nbl_rollout_forward##S, nbl_rollout_backward##S, nbl_rollout_backward_inertia##S,                          \
-   nbl_rollout_checkpoint_bytes##S, nbl_rollout_forward_checkpointed##S, nbl_rollout_backward_checkpointed##S,                               \
-   nbl_selftest_lcp_dantzig_timed##S, nbl_selftest_pinv_rows##S, nbl_set_launch_lanes##S, nbl_set_slices##S, nbl_slices_for##S,               \
-   nbl_set_deferred_join##S, nbl_slice_stream##S, nbl_join_slices##S, nbl_fork_slices##S,                                                                         \
-   nbl_set_timing##S, nbl_get_timing##S, nbl_kernel_timing##S, nbl_contact_readout##S, nbl_contact_readout_rows##S,          \
-   nbl_contact_body_wrenches##S, nbl_task_workspace_bytes##S, nbl_task_jacobian##S, nbl_task_jacobian_deriv##S, nbl_task_jacobian_vjp##S,       \
-   nbl_task_accel##S, nbl_task_accel_vjp##S, nbl_ik_grad_workspace_bytes##S, nbl_ik_solve_vjp##S, nbl_model_tree##S}
+#define NBL_VARIANT(ID, S) {ID, NBL_PER_CAPACITY(NBL_ENTRY, S)}
 constexpr int kNumVariants = 4;
-static const Variant kVariants[kNumVariants] = {NBL_VARIANT_TABLE(8, _c8), NBL_VARIANT_TABLE(16, _c16), NBL_VARIANT_TABLE(64, _c64),
-                                                     NBL_VARIANT_TABLE(128, _c128)};
+static const Variant kVariants[kNumVariants] = {NBL_VARIANT(8, _c8), NBL_VARIANT(16, _c16), NBL_VARIANT(64, _c64), NBL_VARIANT(128, _c128)};
 
 namespace {
 thread_local const Variant* g_errVariant = nullptr;   // whose message nbl_last_error returns: nullptr = the dispatcher's own
@@ -367,38 +299,6 @@ int32_t nbl_contact_readout_rows(nbl_model* m, int64_t B, const void* saved, int
 }
 int32_t nbl_contact_body_wrenches(nbl_model* m, int64_t B, const void* saved, int32_t E, const int32_t* bodies, double* wrench, void* stream) {
   return NBL_FWD(m, contact_body_wrenches, B, saved, E, bodies, wrench, stream);
-}
-
-// ---- task-space Jacobians and accelerations: every instantiation forwards to the one build of nimble_amd_tree.hip, which reports its
-// refusals through ownError like the contact-independent calls (so not NBL_FWD: the text is the dispatcher's own) ----
-#define NBL_TASK(m, FN, ...) (!(m) ? ownError(NBL_E_BADARG, "null model") : (m)->v->FN((m)->impl, ##__VA_ARGS__))
-size_t nbl_task_workspace_bytes(const nbl_model* m, int64_t B) { return NBL_GET(m, task_workspace_bytes, B); }
-int32_t nbl_task_jacobian(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream) {
-  return NBL_TASK(m, task_jacobian, k, B, rows, n, state, J, stream);
-}
-int32_t nbl_task_jacobian_deriv(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
-                                void* stream) {
-  return NBL_TASK(m, task_jacobian_deriv, k, B, rows, n, state, Jdot, stream);
-}
-int32_t nbl_task_jacobian_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
-                              double* grad_q, int32_t accumulate, void* stream) {
-  return NBL_TASK(m, task_jacobian_vjp, k, B, rows, n, state, G, grad_q, accumulate, stream);
-}
-int32_t nbl_task_accel(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
-                       double* bias, double* xdd, void* stream) {
-  return NBL_TASK(m, task_accel, k, B, rows, n, state, accel, bias, xdd, stream);
-}
-int32_t nbl_task_accel_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
-                           const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  return NBL_TASK(m, task_accel_vjp, k, B, rows, n, state, accel, g_out, grad_state, grad_accel, accumulate, workspace, workspace_bytes, stream);
-}
-
-// ---- the reverse pass of inverse kinematics: routed like the task-space entries ----
-size_t nbl_ik_grad_workspace_bytes(const nbl_model* m, const nbl_kin_map* k, int64_t B) { return NBL_GET(m, ik_grad_workspace_bytes, k, B); }
-int32_t nbl_ik_solve_vjp(nbl_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
-                         double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
-  return NBL_TASK(m, ik_solve_vjp, k, B, q, grad_q, grad_damping, grad_target, accumulate, free_count, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// nimble_amd_tree.hip — the contact-independent entry points of include/nimble_amd.h: world-space kinematics, inverse and forward dynamics,
+// nimble_amd_tree.hip — the 43 contact-independent entry points of include/nimble_amd.h: world-space kinematics, inverse and forward dynamics,
 // mass matrix and its inverse, wrenches, contact inverse dynamics, inertia-parameter gradients, IK, centroidal quantities, sensors,
 // task-space Jacobians and accelerations and the reverse pass of IK.
 //
@@ -49,7 +49,8 @@ struct nbl_body_set {
 };
 
 // What every call refuses first, in this order: a missing map or set (`ifNull`: the calls that need one say so), one made on a model of
-// another instantiation, a null model.  The calls' own checks follow.
+// another instantiation, a null model.  The calls' own checks follow.  (The task-space calls and nbl_ik_solve_vjp name a null model before
+// the map, as they always have: handleCheck(h), then mapCheck.)
 static int32_t handleCheck(const nbl_model* h) { return h ? NBL_OK : fail(NBL_E_BADARG, "null model"); }
 static int32_t handleCheck(const nbl_model* h, const nbl_kin_map* k, const char* ifNull) {
   if (!k && ifNull) return fail(NBL_E_BADARG, ifNull);
@@ -61,6 +62,44 @@ static int32_t handleCheck(const nbl_model* h, const nbl_body_set* s) {
   if (h && s->capacity != treeOf(h)->capacity) return fail(NBL_E_BADARG, "the body set was made for another model");
   return handleCheck(h);
 }
+
+// ---- the checks and the launch line the calls below share; each runs after handleCheck, on m = treeOf(h) ----
+static int32_t batchCheck(int64_t B) {   // (B = 0 is not refused: a call that takes it as a no-op returns NBL_OK after this)
+  return B < 0 ? fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")") : NBL_OK;
+}
+static int32_t gridCheck(int64_t B, int block) {
+  return (B + block - 1) / block > (int64_t)0x7fffffff ? fail(NBL_E_BADARG, "B too large for one launch") : NBL_OK;
+}
+// `label`: the family in the message, `fn`: the function that says how many bytes are needed
+static int32_t workspaceCheck(const char* label, const char* fn, int64_t B, const void* workspace, size_t workspace_bytes, size_t need) {
+  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
+  if (workspace_bytes < need)
+    return fail(NBL_E_WORKSPACE, std::string(label) + " workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
+                                     " bytes given, " + fn + "() = " + std::to_string(need));
+  return NBL_OK;
+}
+// a map, wrench set or sensor set that was made for this model; null: `ifNull` says so (nullptr: a set with no entries, accepted)
+static int32_t mapCheck(const nbl_tree_model* m, const nbl_kin_map* k, const char* ifNull = nullptr) {
+  if (!k) return ifNull ? fail(NBL_E_BADARG, ifNull) : NBL_OK;
+  if (k->capacity != m->capacity || k->n != m->n || k->nb != m->nb || k->device != m->device)
+    return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  return NBL_OK;
+}
+// a wrench set or a sensor set (`what`) has whole frames only
+static int32_t spatialCheck(const nbl_kin_map* k, const std::string& what) {
+  for (int e = 0; k && e < k->count; e++)
+    if (k->hEntries[e].kind != KIN_SPATIAL)
+      return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the " + what + " set is not NBL_KIN_SPATIAL: a " + what + " needs a whole frame");
+  return NBL_OK;
+}
+// `kernel` with one world per lane: a 1-D grid of `block`-lane blocks over the B worlds, on the caller's stream (B, stream: the entry point's)
+#define LAUNCH(kernel, block, ...)                                                                                                       \
+  do {                                                                                                                                   \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((B + (block) - 1) / (block))), dim3(block), 0, (hipStream_t)stream, __VA_ARGS__);         \
+    HIP_TRY(hipGetLastError());                                                                                                          \
+  } while (0)
+// the entries, ancestor chains and entry count of a map as the kernels take them; k NULL: a set with no entries
+#define MAP_ARGS(k) (const DevKinEntry*)((k) ? (k)->dEntries : nullptr), (const int32_t*)((k) ? (k)->dPath : nullptr), (int)((k) ? (k)->count : 0)
 
 extern "C" {
 
@@ -134,11 +173,10 @@ void nbl_kin_map_destroy(nbl_kin_map* k) {
 int32_t nbl_kin_map_dim(const nbl_kin_map* k) { return k ? k->P : 0; }
 
 static int32_t kinCheck(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* state) {
-  if (!m || !k || !state) return fail(NBL_E_BADARG, "null argument");
-  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+  if (!state) return fail(NBL_E_BADARG, "null argument");
+  if (const int32_t rc = mapCheck(m, k)) return rc;
   if (B <= 0) return fail(NBL_E_BADARG, "B must be positive");
-  if ((B + KIN_BLOCK - 1) / KIN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  return NBL_OK;
+  return gridCheck(B, KIN_BLOCK);
 }
 
 int32_t nbl_kinematics_forward(nbl_model* h, const nbl_kin_map* k, int64_t B, const double* state, double* pos, double* vel, void* stream) {
@@ -147,9 +185,7 @@ int32_t nbl_kinematics_forward(nbl_model* h, const nbl_kin_map* k, int64_t B, co
   const int32_t rc = kinCheck(m, k, B, state);
   if (rc != NBL_OK) return rc;
   if (!pos && !vel) return NBL_OK;
-  hipLaunchKernelGGL(k_kinematics_fwd, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, pos, vel);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_kinematics_fwd, KIN_BLOCK, (const DevBody*)m->dBodies, MAP_ARGS(k), m->n, B, state, pos, vel);
   return NBL_OK;
 }
 
@@ -160,10 +196,7 @@ int32_t nbl_kinematics_backward(nbl_model* h, const nbl_kin_map* k, int64_t B, c
   const int32_t rc = kinCheck(m, k, B, state);
   if (rc != NBL_OK) return rc;
   if (!grad_state) return fail(NBL_E_BADARG, "null argument");
-  hipLaunchKernelGGL(k_kinematics_vjp, dim3((unsigned)((B + KIN_BLOCK - 1) / KIN_BLOCK)), dim3(KIN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, m->n, B, state, grad_pos,
-                     grad_vel, grad_state, accumulate ? 1 : 0);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_kinematics_vjp, KIN_BLOCK, (const DevBody*)m->dBodies, MAP_ARGS(k), m->n, B, state, grad_pos, grad_vel, grad_state, accumulate ? 1 : 0);
   return NBL_OK;
 }
 
@@ -174,18 +207,22 @@ static size_t dynWorkspaceBytes(const nbl_tree_model* m, int64_t B) {
 }
 size_t nbl_dynamics_workspace_bytes(const nbl_model* h, int64_t B) { return h ? dynWorkspaceBytes(treeOf(h), B) : 0; }
 
-static int32_t dynCheck(const nbl_tree_model* m, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+// workspace of the forward-dynamics calls: [nb][FD_SLOTS][B] tree slots (the reverse pass's k_inverse_dynamics_vjp reuses them: DYN_SLOTS <=
+// FD_SLOTS), then the recomputed acceleration [n][B] and -lambda [n][B] of nbl_forward_dynamics_backward
+static_assert(DYN_SLOTS <= FD_SLOTS, "the reverse pass runs k_inverse_dynamics_vjp on the forward-dynamics tree slots");
+static size_t fdynWorkspaceBytes(const nbl_tree_model* m, int64_t B) {
+  if (!m || B <= 0) return 0;
+  return sizeof(double) * ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
+}
+
+// the checks of the dynamics calls without a wrench set; fd: a forward-dynamics call (its workspace is the larger one)
+static int32_t dynCheck(const nbl_tree_model* m, bool fd, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
+  if (const int32_t rc = batchCheck(B)) return rc;
   if (B == 0) return NBL_OK;
   if (!state || !out) return fail(NBL_E_BADARG, "null argument");
-  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = dynWorkspaceBytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "dynamics workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_dynamics_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
+  if (const int32_t rc = gridCheck(B, DYN_BLOCK)) return rc;
+  return fd ? workspaceCheck("forward-dynamics", "nbl_forward_dynamics_workspace_bytes", B, workspace, workspace_bytes, fdynWorkspaceBytes(m, B))
+            : workspaceCheck("dynamics", "nbl_dynamics_workspace_bytes", B, workspace, workspace_bytes, dynWorkspaceBytes(m, B));
 }
 static int32_t dynFlags(int32_t flags) {
   if (flags & ~DYN_FLAG_MASK) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~DYN_FLAG_MASK) + " (NBL_ID_*)");
@@ -196,13 +233,12 @@ int32_t nbl_inverse_dynamics_forward(nbl_model* h, int64_t B, const double* stat
                                      void* workspace, size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  int32_t rc = dynCheck(m, B, state, tau, workspace, workspace_bytes);
+  int32_t rc = dynCheck(m, false, B, state, tau, workspace, workspace_bytes);
   if (rc == NBL_OK) rc = dynFlags(flags);
   if (rc != NBL_OK || B == 0) return rc;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, tau, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_inverse_dynamics, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, tau,
+         (double*)workspace);
   return NBL_OK;
 }
 
@@ -211,66 +247,40 @@ int32_t nbl_inverse_dynamics_backward(nbl_model* h, int64_t B, const double* sta
                                       size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  int32_t rc = dynCheck(m, B, state, grad_tau, workspace, workspace_bytes);
+  int32_t rc = dynCheck(m, false, B, state, grad_tau, workspace, workspace_bytes);
   if (rc == NBL_OK) rc = dynFlags(flags);
   if (rc != NBL_OK || B == 0) return rc;
   if (!grad_state && !grad_accel) return NBL_OK;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, grad_tau, grad_state, grad_accel,
-                     accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_inverse_dynamics_vjp, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, grad_tau,
+         grad_state, grad_accel, accumulate ? 1 : 0, (double*)workspace);
   return NBL_OK;
 }
 
 int32_t nbl_mass_matrix(nbl_model* h, int64_t B, const double* state, double* M, void* workspace, size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  const int32_t rc = dynCheck(m, B, state, M, workspace, workspace_bytes);
+  const int32_t rc = dynCheck(m, false, B, state, M, workspace, workspace_bytes);
   if (rc != NBL_OK || B == 0) return rc;
   DeviceGuard guard(m->device);
   HIP_TRY(hipMemsetAsync(M, 0, sizeof(double) * (size_t)m->n * m->n * (size_t)B, (hipStream_t)stream));   // unrelated DOFs: the kernel writes the rest
-  hipLaunchKernelGGL(k_mass_matrix, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, B, state, M, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_mass_matrix, DYN_BLOCK, (const DevBody*)m->dBodies, m->mdl, B, state, M, (double*)workspace);
   return NBL_OK;
 }
 
 // ---- forward dynamics and the inverse mass matrix (articulated-body algorithm; csrc/dynamics.hip) ---------------------------------------
-// workspace: [nb][FD_SLOTS][B] tree slots (the reverse pass's k_inverse_dynamics_vjp reuses them: DYN_SLOTS <= FD_SLOTS), then the
-// recomputed acceleration [n][B] and -lambda [n][B] of nbl_forward_dynamics_backward
-static_assert(DYN_SLOTS <= FD_SLOTS, "the reverse pass runs k_inverse_dynamics_vjp on the forward-dynamics tree slots");
-static size_t fdynWorkspaceBytes(const nbl_tree_model* m, int64_t B) {
-  if (!m || B <= 0) return 0;
-  return sizeof(double) * ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
-}
 size_t nbl_forward_dynamics_workspace_bytes(const nbl_model* h, int64_t B) { return h ? fdynWorkspaceBytes(treeOf(h), B) : 0; }
-
-static int32_t fdynCheck(const nbl_tree_model* m, int64_t B, const double* state, const void* out, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (B == 0) return NBL_OK;
-  if (!state || !out) return fail(NBL_E_BADARG, "null argument");
-  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = fdynWorkspaceBytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "forward-dynamics workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_forward_dynamics_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
-}
 
 int32_t nbl_forward_dynamics_forward(nbl_model* h, int64_t B, const double* state, const double* tau, int32_t flags, double* accel,
                                      void* workspace, size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  int32_t rc = fdynCheck(m, B, state, accel, workspace, workspace_bytes);
+  int32_t rc = dynCheck(m, true, B, state, accel, workspace, workspace_bytes);
   if (rc == NBL_OK) rc = dynFlags(flags);
   if (rc != NBL_OK || B == 0) return rc;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_forward_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, accel, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_forward_dynamics, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, accel,
+         (double*)workspace);
   return NBL_OK;
 }
 
@@ -279,7 +289,7 @@ int32_t nbl_forward_dynamics_backward(nbl_model* h, int64_t B, const double* sta
                                       void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  int32_t rc = fdynCheck(m, B, state, grad_accel, workspace, workspace_bytes);
+  int32_t rc = dynCheck(m, true, B, state, grad_accel, workspace, workspace_bytes);
   if (rc == NBL_OK) rc = dynFlags(flags);
   if (rc != NBL_OK || B == 0) return rc;
   if (!grad_state && !grad_tau) return NBL_OK;
@@ -287,14 +297,11 @@ int32_t nbl_forward_dynamics_backward(nbl_model* h, int64_t B, const double* sta
   double* ws = (double*)workspace;
   double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
   double* neglam = accel + (size_t)m->n * (size_t)B;
-  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
-  hipLaunchKernelGGL(k_forward_dynamics_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
-                     m->mdl, (int)flags, B, state, tau, grad_accel, accel, neglam, grad_tau, accumulate ? 1 : 0, ws);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_forward_dynamics_lambda, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, grad_accel,
+         accel, neglam, grad_tau, accumulate ? 1 : 0, ws);
   if (grad_state) {   // grad_state (+)= -(d ID / d [q; v])^T lambda at (q, v, a): inverse dynamics is the exact inverse function
-    hipLaunchKernelGGL(k_inverse_dynamics_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
-                       m->mdl, (int)flags, B, state, (const double*)accel, (const double*)neglam, grad_state, (double*)nullptr, accumulate ? 1 : 0, ws);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_inverse_dynamics_vjp, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, (const double*)accel,
+           (const double*)neglam, grad_state, (double*)nullptr, accumulate ? 1 : 0, ws);
   }
   return NBL_OK;
 }
@@ -303,27 +310,23 @@ int32_t nbl_inv_mass_apply(nbl_model* h, int64_t B, int32_t R, const double* sta
                            size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  const int32_t rc = fdynCheck(m, B, state, Y, workspace, workspace_bytes);
+  const int32_t rc = dynCheck(m, true, B, state, Y, workspace, workspace_bytes);
   if (rc != NBL_OK) return rc;
   if (R < 1) return fail(NBL_E_BADARG, "R must be at least 1 (got " + std::to_string(R) + ")");
   if (B == 0) return NBL_OK;
   if (!X && R != m->n) return fail(NBL_E_BADARG, "X may be null (the identity) only with R = n");
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, B, (int)R, state, X, Y, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_minv_apply, DYN_BLOCK, (const DevBody*)m->dBodies, m->mdl, B, (int)R, state, X, Y, (double*)workspace);
   return NBL_OK;
 }
 
 int32_t nbl_inv_mass_matrix(nbl_model* h, int64_t B, const double* state, double* Minv, void* workspace, size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  const int32_t rc = fdynCheck(m, B, state, Minv, workspace, workspace_bytes);
+  const int32_t rc = dynCheck(m, true, B, state, Minv, workspace, workspace_bytes);
   if (rc != NBL_OK || B == 0) return rc;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_minv_apply, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, B, (int)m->n, state, (const double*)nullptr, Minv, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_minv_apply, DYN_BLOCK, (const DevBody*)m->dBodies, m->mdl, B, (int)m->n, state, (const double*)nullptr, Minv, (double*)workspace);
   return NBL_OK;
 }
 
@@ -342,26 +345,16 @@ size_t nbl_wrench_workspace_bytes(const nbl_model* h, const nbl_kin_map* k, int6
 // the checks the wrench calls share; k NULL: a set with no entries
 static int32_t wrenchCheck(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* state, const void* out, const double* wrench,
                            int32_t flags, int32_t flagMask, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (k && (k->n != m->n || k->nb != m->nb || k->device != m->device)) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  if (k)
-    for (int e = 0; e < k->count; e++)
-      if (k->hEntries[e].kind != KIN_SPATIAL)
-        return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the wrench set is not NBL_KIN_SPATIAL: a wrench needs a whole frame");
+  if (const int32_t rc = mapCheck(m, k)) return rc;
+  if (const int32_t rc = spatialCheck(k, "wrench")) return rc;
   if (flags & ~flagMask) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~flagMask) + " (NBL_ID_*, NBL_WRENCH_WORLD)");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (const int32_t rc = batchCheck(B)) return rc;
   if (B == 0) return NBL_OK;
   if (!state || !out) return fail(NBL_E_BADARG, "null argument");
   if (k && !wrench) return fail(NBL_E_BADARG, "null wrench array for a set of " + std::to_string(k->count) + " entries");
-  if ((B + DYN_BLOCK - 1) / DYN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = wrenchWorkspaceBytes(m, k, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "wrench workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_wrench_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
+  if (const int32_t rc = gridCheck(B, DYN_BLOCK)) return rc;
+  return workspaceCheck("wrench", "nbl_wrench_workspace_bytes", B, workspace, workspace_bytes, wrenchWorkspaceBytes(m, k, B));
 }
-#define NBL_WRENCH_SET(k) (const DevKinEntry*)((k) ? (k)->dEntries : nullptr), (const int32_t*)((k) ? (k)->dPath : nullptr), (int)wrenchCount(k)
 
 int32_t nbl_inverse_dynamics_wrench_forward(nbl_model* h, const nbl_kin_map* k, int64_t B, const double* state, const double* accel,
                                             const double* wrench, int32_t flags, double* tau, void* workspace, size_t workspace_bytes,
@@ -371,10 +364,8 @@ int32_t nbl_inverse_dynamics_wrench_forward(nbl_model* h, const nbl_kin_map* k, 
   const int32_t rc = wrenchCheck(m, k, B, state, tau, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
   if (rc != NBL_OK || B == 0) return rc;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics_wrench, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, NBL_WRENCH_SET(k), wrench, tau,
-                     (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_inverse_dynamics_wrench, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, MAP_ARGS(k),
+         wrench, tau, (double*)workspace);
   return NBL_OK;
 }
 
@@ -389,10 +380,8 @@ int32_t nbl_inverse_dynamics_wrench_backward(nbl_model* h, const nbl_kin_map* k,
   DeviceGuard guard(m->device);
   double* ws = (double*)workspace;
   double* wx = ws + ((size_t)m->nb * FD_SLOTS + 2 * (size_t)m->n) * (size_t)B;
-  hipLaunchKernelGGL(k_inverse_dynamics_wrench_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel, NBL_WRENCH_SET(k), wrench, grad_tau,
-                     grad_state, grad_accel, grad_wrench, accumulate ? 1 : 0, ws, wx);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_inverse_dynamics_wrench_vjp, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, accel,
+         MAP_ARGS(k), wrench, grad_tau, grad_state, grad_accel, grad_wrench, accumulate ? 1 : 0, ws, wx);
   return NBL_OK;
 }
 
@@ -404,10 +393,8 @@ int32_t nbl_forward_dynamics_wrench_forward(nbl_model* h, const nbl_kin_map* k, 
   const int32_t rc = wrenchCheck(m, k, B, state, accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
   if (rc != NBL_OK || B == 0) return rc;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_forward_dynamics_wrench, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, accel,
-                     (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_forward_dynamics_wrench, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, MAP_ARGS(k),
+         wrench, accel, (double*)workspace);
   return NBL_OK;
 }
 
@@ -424,16 +411,11 @@ int32_t nbl_forward_dynamics_wrench_backward(nbl_model* h, const nbl_kin_map* k,
   double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
   double* neglam = accel + (size_t)m->n * (size_t)B;
   double* wx = neglam + (size_t)m->n * (size_t)B;
-  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
-  hipLaunchKernelGGL(k_forward_dynamics_wrench_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
-                     (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, grad_accel, accel, neglam, grad_tau,
-                     accumulate ? 1 : 0, ws);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_forward_dynamics_wrench_lambda, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau,
+         MAP_ARGS(k), wrench, grad_accel, accel, neglam, grad_tau, accumulate ? 1 : 0, ws);
   if (grad_state || grad_wrench) {   // grad_state (+)= -(d ID / d [q; v])^T lambda, grad_wrench (+)= J lambda, at (q, v, a) with the same wrenches
-    hipLaunchKernelGGL(k_inverse_dynamics_wrench_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
-                       (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, (const double*)accel, NBL_WRENCH_SET(k), wrench, (const double*)neglam,
-                       grad_state, (double*)nullptr, grad_wrench, accumulate ? 1 : 0, ws, wx);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_inverse_dynamics_wrench_vjp, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state,
+           (const double*)accel, MAP_ARGS(k), wrench, (const double*)neglam, grad_state, (double*)nullptr, grad_wrench, accumulate ? 1 : 0, ws, wx);
   }
   return NBL_OK;
 }
@@ -445,15 +427,13 @@ int32_t nbl_inverse_dynamics_backward_inertia(nbl_model* h, int64_t B, const dou
                                               size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h)) return refused;
   nbl_tree_model* const m = treeOf(h);
-  int32_t rc = dynCheck(m, B, state, grad_tau, workspace, workspace_bytes);
+  int32_t rc = dynCheck(m, false, B, state, grad_tau, workspace, workspace_bytes);
   if (rc == NBL_OK) rc = dynFlags(flags);
   if (rc != NBL_OK || B == 0 || m->nParams == 0) return rc;
   if (!grad_params) return fail(NBL_E_BADARG, "null grad_params for " + std::to_string(m->nParams) + " registered inertia parameters");
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_inverse_dynamics_inertia_vjp, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, (int)flags, B, state, accel, grad_tau, (const DevInertiaParam*)m->dParams, m->nParams,
-                     grad_params, accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_inverse_dynamics_inertia_vjp, DYN_BLOCK, (const DevBody*)m->dBodies, m->mdl, (int)flags, B, state, accel, grad_tau,
+         (const DevInertiaParam*)m->dParams, m->nParams, grad_params, accumulate ? 1 : 0, (double*)workspace);
   return NBL_OK;
 }
 
@@ -468,7 +448,7 @@ int32_t nbl_forward_dynamics_backward_inertia(nbl_model* h, const nbl_kin_map* k
   if (k) {
     rc = wrenchCheck(m, k, B, state, grad_accel, wrench, flags, DYN_FLAG_MASK | DYN_WRENCH_WORLD, workspace, workspace_bytes);
   } else {
-    rc = fdynCheck(m, B, state, grad_accel, workspace, workspace_bytes);
+    rc = dynCheck(m, true, B, state, grad_accel, workspace, workspace_bytes);
     if (rc == NBL_OK) rc = dynFlags(flags);
   }
   if (rc != NBL_OK || B == 0 || m->nParams == 0) return rc;
@@ -477,19 +457,14 @@ int32_t nbl_forward_dynamics_backward_inertia(nbl_model* h, const nbl_kin_map* k
   double* ws = (double*)workspace;
   double* accel = ws + (size_t)m->nb * FD_SLOTS * (size_t)B;
   double* neglam = accel + (size_t)m->n * (size_t)B;
-  const dim3 grid((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK));
   if (k)
-    hipLaunchKernelGGL(k_forward_dynamics_wrench_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies,
-                       (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, NBL_WRENCH_SET(k), wrench, grad_accel, accel, neglam,
-                       (double*)nullptr, 0, ws);
+    LAUNCH(k_forward_dynamics_wrench_lambda, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau,
+           MAP_ARGS(k), wrench, grad_accel, accel, neglam, (double*)nullptr, 0, ws);
   else
-    hipLaunchKernelGGL(k_forward_dynamics_lambda, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs,
-                       m->mdl, (int)flags, B, state, tau, grad_accel, accel, neglam, (double*)nullptr, 0, ws);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_inverse_dynamics_inertia_vjp, grid, dim3(DYN_BLOCK), 0, (hipStream_t)stream, (const DevBody*)m->dBodies, m->mdl,
-                     (int)(flags & DYN_FLAG_MASK), B, state, (const double*)accel, (const double*)neglam, (const DevInertiaParam*)m->dParams,
-                     m->nParams, grad_params, accumulate ? 1 : 0, ws);
-  HIP_TRY(hipGetLastError());
+    LAUNCH(k_forward_dynamics_lambda, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, B, state, tau, grad_accel,
+           accel, neglam, (double*)nullptr, 0, ws);
+  LAUNCH(k_inverse_dynamics_inertia_vjp, DYN_BLOCK, (const DevBody*)m->dBodies, m->mdl, (int)(flags & DYN_FLAG_MASK), B, state, (const double*)accel,
+         (const double*)neglam, (const DevInertiaParam*)m->dParams, m->nParams, grad_params, accumulate ? 1 : 0, ws);
   return NBL_OK;
 }
 
@@ -515,10 +490,8 @@ int32_t nbl_contact_inverse_dynamics(nbl_model* h, const nbl_kin_map* k, int64_t
   DeviceGuard guard(m->device);
   double* ws = (double*)workspace;
   double* xs = ws + ((size_t)m->nb * (FD_SLOTS + 3) + 2 * (size_t)m->n) * (size_t)B;
-  hipLaunchKernelGGL(k_contact_inverse_dynamics, dim3((unsigned)((B + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, (int)mode, B, state, accel, NBL_WRENCH_SET(k),
-                     mode == NBL_CID_NEAREST ? wrench_guess : (const double*)nullptr, wrench_out, tau, ws, xs);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_contact_inverse_dynamics, DYN_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, m->mdl, (int)flags, (int)mode, B, state, accel,
+         MAP_ARGS(k), mode == NBL_CID_NEAREST ? wrench_guess : (const double*)nullptr, wrench_out, tau, ws, xs);
   return NBL_OK;
 }
 
@@ -541,9 +514,8 @@ int32_t nbl_ik_solve(nbl_model* h, const nbl_kin_map* k, int64_t B, const double
                      double* q_out, double* loss, int32_t* steps, void* workspace, size_t workspace_bytes, void* stream) {
   if (const int32_t refused = handleCheck(h, k, "null kinematics map")) return refused;
   nbl_tree_model* const m = treeOf(h);
-  if (!m || !k) return fail(NBL_E_BADARG, "null argument");
-  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (const int32_t rc = mapCheck(m, k)) return rc;
+  if (const int32_t rc = batchCheck(B)) return rc;
   IkConfig cfg;
   if (config) {
     cfg.convergenceThreshold = config->convergence_threshold; cfg.maxStepCount = config->max_step_count;
@@ -561,16 +533,33 @@ int32_t nbl_ik_solve(nbl_model* h, const nbl_kin_map* k, int64_t B, const double
     return fail(NBL_E_UNSUPPORTED, "least_squares_damping = 0 (the reference's complete orthogonal decomposition) is outside the device path");
   if (B == 0) return NBL_OK;
   if (!target || !q_out || !workspace) return fail(NBL_E_BADARG, "null argument");
-  if ((B + IK_BLOCK - 1) / IK_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = ikWorkspaceBytes(m, k, B);
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "IK workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_ik_workspace_bytes() = " + std::to_string(need));
+  if (const int32_t rc = gridCheck(B, IK_BLOCK)) return rc;
+  if (const int32_t rc = workspaceCheck("IK", "nbl_ik_workspace_bytes", B, workspace, workspace_bytes, ikWorkspaceBytes(m, k, B))) return rc;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_ik_solve, dim3((unsigned)((B + IK_BLOCK - 1) / IK_BLOCK)), dim3(IK_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
-                     m->nb, m->n, k->P, B, target, q_init, cfg, q_out, loss, steps, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_ik_solve, IK_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, MAP_ARGS(k), m->nb, m->n, k->P, B, target, q_init, cfg, q_out,
+         loss, steps, (double*)workspace);
+  return NBL_OK;
+}
+
+// ---- the reverse pass of inverse kinematics (csrc/ik_grad.hip); its scratch has the solver's layout: J, the normal matrix, three vectors ----
+size_t nbl_ik_grad_workspace_bytes(const nbl_model* h, const nbl_kin_map* k, int64_t B) { return nbl_ik_workspace_bytes(h, k, B); }
+
+int32_t nbl_ik_solve_vjp(nbl_model* h, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
+                         double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (const int32_t refused = handleCheck(h)) return refused;   // (a null model before a null map, unlike nbl_ik_solve)
+  nbl_tree_model* const m = treeOf(h);
+  if (const int32_t rc = mapCheck(m, k, "null kinematics map")) return rc;
+  if (const int32_t rc = batchCheck(B)) return rc;
+  if (!(grad_damping >= 0.0)) return fail(NBL_E_BADARG, "grad_damping must not be negative");
+  if (grad_damping == 0.0)
+    return fail(NBL_E_UNSUPPORTED, "grad_damping = 0 (a pseudo-inverse of a possibly singular Jacobian) is outside the device path");
+  if (B == 0) return NBL_OK;
+  if (!q || !grad_q || !grad_target || !workspace) return fail(NBL_E_BADARG, "null argument");
+  if (const int32_t rc = gridCheck(B, IK_GRAD_BLOCK)) return rc;
+  if (const int32_t rc = workspaceCheck("IK gradient", "nbl_ik_grad_workspace_bytes", B, workspace, workspace_bytes, ikWorkspaceBytes(m, k, B))) return rc;
+  DeviceGuard guard(m->device);
+  LAUNCH(k_ik_solve_vjp, IK_GRAD_BLOCK, (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, MAP_ARGS(k), m->nb, m->n, k->P, B, q, grad_q,
+         grad_damping, grad_target, accumulate ? 1 : 0, free_count, (double*)workspace);
   return NBL_OK;
 }
 
@@ -644,21 +633,14 @@ size_t nbl_centroidal_workspace_bytes(const nbl_model* h, int64_t B) { return h 
 
 static int32_t cenCheck(const nbl_tree_model* m, const nbl_body_set* s, int64_t B, const double* state, int32_t flags, const void* workspace,
                         size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (!s) return fail(NBL_E_BADARG, "null body set");
   if (s->n != m->n || s->nb != m->nb || s->device != m->device) return fail(NBL_E_BADARG, "the body set was made for another model");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (const int32_t rc = batchCheck(B)) return rc;
   if (flags & ~CEN_FLAG_MASK) return fail(NBL_E_BADARG, "unknown flag bits " + std::to_string(flags & ~CEN_FLAG_MASK) + " (NBL_CEN_*)");
   if (B == 0) return NBL_OK;
   if (!state) return fail(NBL_E_BADARG, "null argument");
-  if ((B + CEN_BLOCK - 1) / CEN_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
+  if (const int32_t rc = gridCheck(B, CEN_BLOCK)) return rc;
   if (!(cenTotalMass(m->hBodies.data(), m->nb, s->set.mass) > 0.0)) return fail(NBL_E_BADARG, "the body set has no mass");
-  const size_t need = cenWorkspaceBytes(m, B);
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "centroidal workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_centroidal_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
+  return workspaceCheck("centroidal", "nbl_centroidal_workspace_bytes", B, workspace, workspace_bytes, cenWorkspaceBytes(m, B));
 }
 
 int32_t nbl_centroidal_forward(nbl_model* h, const nbl_body_set* set, int64_t B, const double* state, const double* accel, int32_t flags,
@@ -708,22 +690,13 @@ size_t nbl_sensors_workspace_bytes(const nbl_model* h, int64_t B) { return nbl_c
 
 // the checks the two sensor calls share; a sensor set is a kinematics map of NBL_KIN_SPATIAL entries, like a wrench set
 static int32_t sensCheck(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* state, const void* workspace, size_t workspace_bytes) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (!k) return fail(NBL_E_BADARG, "null sensor set");
-  if (k->n != m->n || k->nb != m->nb || k->device != m->device) return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  for (int e = 0; e < k->count; e++)
-    if (k->hEntries[e].kind != KIN_SPATIAL)
-      return fail(NBL_E_BADARG, "entry " + std::to_string(e) + " of the sensor set is not NBL_KIN_SPATIAL: a sensor needs a whole frame");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (const int32_t rc = mapCheck(m, k)) return rc;
+  if (const int32_t rc = spatialCheck(k, "sensor")) return rc;
+  if (const int32_t rc = batchCheck(B)) return rc;
   if (B == 0) return NBL_OK;
   if (!state) return fail(NBL_E_BADARG, "null argument");
-  if ((B + SENS_BLOCK - 1) / SENS_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = cenWorkspaceBytes(m, B);   // (= nbl_sensors_workspace_bytes)
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "sensor workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_sensors_workspace_bytes() = " + std::to_string(need));
-  return NBL_OK;
+  if (const int32_t rc = gridCheck(B, SENS_BLOCK)) return rc;
+  return workspaceCheck("sensor", "nbl_sensors_workspace_bytes", B, workspace, workspace_bytes, cenWorkspaceBytes(m, B));
 }
 
 int32_t nbl_sensors_forward(nbl_model* h, const nbl_kin_map* k, int64_t B, const double* state, const double* accel, const double* field,
@@ -736,10 +709,7 @@ int32_t nbl_sensors_forward(nbl_model* h, const nbl_kin_map* k, int64_t B, const
   if (mag && !field) return fail(NBL_E_BADARG, "mag needs the magnetic field (field is null)");
   if (B == 0 || !(gyro || acc || mag)) return NBL_OK;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_sensors, dim3((unsigned)((B + SENS_BLOCK - 1) / SENS_BLOCK)), dim3(SENS_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, B, state, accel, field,
-                     gyro, acc, mag, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_sensors, SENS_BLOCK, (const DevBody*)m->dBodies, m->mdl, MAP_ARGS(k), B, state, accel, field, gyro, acc, mag, (double*)workspace);
   return NBL_OK;
 }
 
@@ -754,136 +724,86 @@ int32_t nbl_sensors_backward(nbl_model* h, const nbl_kin_map* k, int64_t B, cons
   if (g_mag && !field) return fail(NBL_E_BADARG, "g_mag needs the magnetic field (field is null)");
   if (B == 0 || (!grad_state && !grad_accel && !grad_field)) return NBL_OK;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_sensors_vjp, dim3((unsigned)((B + SENS_BLOCK - 1) / SENS_BLOCK)), dim3(SENS_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count, B, state, accel, field,
-                     g_gyro, g_acc, g_mag, grad_state, grad_accel, grad_field, accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_sensors_vjp, SENS_BLOCK, (const DevBody*)m->dBodies, m->mdl, MAP_ARGS(k), B, state, accel, field, g_gyro, g_acc, g_mag, grad_state,
+         grad_accel, grad_field, accumulate ? 1 : 0, (double*)workspace);
   return NBL_OK;
 }
-
-}  // extern "C"
 
 // ---- task-space Jacobians, their time derivative and task-space accelerations (csrc/taskspace.hip) ------------------------------------------
-// The kernels are built once, here; the entry points nbl_task_* of include/nimble_amd.h exist per instantiation (nimble_amd.hip, renamed by
-// abi_variants.h, routed by the dispatcher) as thin forwards to the functions below on the handle's base (tree_model_host.hpp declares them).
-size_t treeTaskWorkspaceBytes(const nbl_tree_model* m, int64_t B) { return cenWorkspaceBytes(m, B); }
+size_t nbl_task_workspace_bytes(const nbl_model* h, int64_t B) { return nbl_centroidal_workspace_bytes(h, B); }
 
-// the checks the five calls share
-static int32_t taskCheck(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (!k) return fail(NBL_E_BADARG, "null kinematics map");
-  if (k->capacity != m->capacity || k->n != m->n || k->nb != m->nb || k->device != m->device)
-    return fail(NBL_E_BADARG, "the kinematics map was made for another model");
+// the checks the five calls share: a null model first, then the map
+static int32_t taskCheck(const nbl_model* h, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state) {
+  if (const int32_t refused = handleCheck(h)) return refused;
+  const nbl_tree_model* const m = treeOf(h);
+  if (const int32_t rc = mapCheck(m, k, "null kinematics map")) return rc;
   if (rows != k->P) return fail(NBL_E_BADARG, "rows = " + std::to_string(rows) + ", the kinematics map has " + std::to_string(k->P));
   if (n != m->n) return fail(NBL_E_BADARG, "n = " + std::to_string(n) + ", the model has " + std::to_string(m->n) + " DOFs");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
+  if (const int32_t rc = batchCheck(B)) return rc;
   if (B == 0) return NBL_OK;
   if (!state) return fail(NBL_E_BADARG, "null argument");
-  if ((B + TASK_BLOCK - 1) / TASK_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  return NBL_OK;
+  return gridCheck(B, TASK_BLOCK);
 }
-#define TASK_GRID(B) dim3((unsigned)(((B) + TASK_BLOCK - 1) / TASK_BLOCK)), dim3(TASK_BLOCK), 0, (hipStream_t)stream
 
-int32_t treeTaskJacobian(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream) {
-  const int32_t rc = taskCheck(m, k, B, rows, n, state);
-  if (rc != NBL_OK) return rc;
-  if (B == 0) return NBL_OK;
+int32_t nbl_task_jacobian(nbl_model* h, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream) {
+  const int32_t rc = taskCheck(h, k, B, rows, n, state);
+  if (rc != NBL_OK || B == 0) return rc;
   if (!J) return fail(NBL_E_BADARG, "null argument");
+  nbl_tree_model* const m = treeOf(h);
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_task_jacobian, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
-                     m->n, B, state, J);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_task_jacobian, TASK_BLOCK, (const DevBody*)m->dBodies, MAP_ARGS(k), m->n, B, state, J);
   return NBL_OK;
 }
 
-int32_t treeTaskJacobianDeriv(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
+int32_t nbl_task_jacobian_deriv(nbl_model* h, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
                                 void* stream) {
-  const int32_t rc = taskCheck(m, k, B, rows, n, state);
-  if (rc != NBL_OK) return rc;
-  if (B == 0) return NBL_OK;
+  const int32_t rc = taskCheck(h, k, B, rows, n, state);
+  if (rc != NBL_OK || B == 0) return rc;
   if (!Jdot) return fail(NBL_E_BADARG, "null argument");
+  nbl_tree_model* const m = treeOf(h);
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_task_jacobian_deriv, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath,
-                     k->count, m->n, B, state, Jdot);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_task_jacobian_deriv, TASK_BLOCK, (const DevBody*)m->dBodies, MAP_ARGS(k), m->n, B, state, Jdot);
   return NBL_OK;
 }
 
-int32_t treeTaskJacobianVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
+int32_t nbl_task_jacobian_vjp(nbl_model* h, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
                               double* grad_q, int32_t accumulate, void* stream) {
-  const int32_t rc = taskCheck(m, k, B, rows, n, state);
-  if (rc != NBL_OK) return rc;
-  if (B == 0) return NBL_OK;
+  const int32_t rc = taskCheck(h, k, B, rows, n, state);
+  if (rc != NBL_OK || B == 0) return rc;
   if (!G || !grad_q) return fail(NBL_E_BADARG, "null argument");
+  nbl_tree_model* const m = treeOf(h);
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_task_jacobian_vjp, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath,
-                     k->count, m->n, B, state, G, grad_q, accumulate ? 1 : 0);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_task_jacobian_vjp, TASK_BLOCK, (const DevBody*)m->dBodies, MAP_ARGS(k), m->n, B, state, G, grad_q, accumulate ? 1 : 0);
   return NBL_OK;
 }
 
-int32_t treeTaskAccel(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+int32_t nbl_task_accel(nbl_model* h, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
                        double* bias, double* xdd, void* stream) {
-  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  const int32_t rc = taskCheck(h, k, B, rows, n, state);
   if (rc != NBL_OK) return rc;
   if (xdd && !accel) return fail(NBL_E_BADARG, "xdd needs the accelerations (accel is null)");
   if (B == 0 || (!bias && !xdd)) return NBL_OK;
+  nbl_tree_model* const m = treeOf(h);
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_task_accel, TASK_GRID(B), (const DevBody*)m->dBodies, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
-                     m->n, B, state, accel, bias, xdd);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_task_accel, TASK_BLOCK, (const DevBody*)m->dBodies, MAP_ARGS(k), m->n, B, state, accel, bias, xdd);
   return NBL_OK;
 }
 
-int32_t treeTaskAccelVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
+int32_t nbl_task_accel_vjp(nbl_model* h, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
                            const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
                            size_t workspace_bytes, void* stream) {
-  const int32_t rc = taskCheck(m, k, B, rows, n, state);
+  const int32_t rc = taskCheck(h, k, B, rows, n, state);
   if (rc != NBL_OK) return rc;
   if (grad_accel && !accel) return fail(NBL_E_BADARG, "grad_accel needs the accelerations (accel is null)");
   if (B == 0 || (!grad_state && !grad_accel)) return NBL_OK;
   if (!g_out) return fail(NBL_E_BADARG, "null argument");
-  const size_t need = cenWorkspaceBytes(m, B);   // (= nbl_task_workspace_bytes)
-  if (!workspace) return fail(NBL_E_BADARG, "null workspace");
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "task-space workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_task_workspace_bytes() = " + std::to_string(need));
+  nbl_tree_model* const m = treeOf(h);
+  if (const int32_t refused = workspaceCheck("task-space", "nbl_task_workspace_bytes", B, workspace, workspace_bytes, cenWorkspaceBytes(m, B)))
+    return refused;
   DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_task_accel_vjp, TASK_GRID(B), (const DevBody*)m->dBodies, m->mdl, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath,
-                     k->count, B, state, accel, g_out, grad_state, grad_accel, accumulate ? 1 : 0, (double*)workspace);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(k_task_accel_vjp, TASK_BLOCK, (const DevBody*)m->dBodies, m->mdl, MAP_ARGS(k), B, state, accel, g_out, grad_state, grad_accel,
+         accumulate ? 1 : 0, (double*)workspace);
   return NBL_OK;
 }
-#undef TASK_GRID
 
-// ---- the reverse pass of inverse kinematics (csrc/ik_grad.hip) ----------------------------------------------------------------------------
-// Built once, here, and reached like the task-space calls: nbl_ik_grad_workspace_bytes / nbl_ik_solve_vjp of include/nimble_amd.h are thin
-// forwards in every instantiation (nimble_amd.hip) to the two functions below on the handle's base (tree_model_host.hpp declares them).
-size_t treeIkGradWorkspaceBytes(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B) {
-  return (m && k && k->capacity == m->capacity) ? ikWorkspaceBytes(m, k, B) : 0;   // the solver's layout: J, the normal matrix, three vectors
-}
-
-int32_t treeIkSolveVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
-                       double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m) return fail(NBL_E_BADARG, "null model handle");
-  if (!k) return fail(NBL_E_BADARG, "null kinematics map");
-  if (k->capacity != m->capacity || k->n != m->n || k->nb != m->nb || k->device != m->device)
-    return fail(NBL_E_BADARG, "the kinematics map was made for another model");
-  if (B < 0) return fail(NBL_E_BADARG, "B must not be negative (got " + std::to_string(B) + ")");
-  if (!(grad_damping >= 0.0)) return fail(NBL_E_BADARG, "grad_damping must not be negative");
-  if (grad_damping == 0.0)
-    return fail(NBL_E_UNSUPPORTED, "grad_damping = 0 (a pseudo-inverse of a possibly singular Jacobian) is outside the device path");
-  if (B == 0) return NBL_OK;
-  if (!q || !grad_q || !grad_target || !workspace) return fail(NBL_E_BADARG, "null argument");
-  if ((B + IK_GRAD_BLOCK - 1) / IK_GRAD_BLOCK > (int64_t)0x7fffffff) return fail(NBL_E_BADARG, "B too large for one launch");
-  const size_t need = ikWorkspaceBytes(m, k, B);
-  if (workspace_bytes < need)
-    return fail(NBL_E_WORKSPACE, "IK gradient workspace too small for B = " + std::to_string(B) + ": " + std::to_string(workspace_bytes) +
-                                     " bytes given, nbl_ik_grad_workspace_bytes() = " + std::to_string(need));
-  DeviceGuard guard(m->device);
-  hipLaunchKernelGGL(k_ik_solve_vjp, dim3((unsigned)((B + IK_GRAD_BLOCK - 1) / IK_GRAD_BLOCK)), dim3(IK_GRAD_BLOCK), 0, (hipStream_t)stream,
-                     (const DevBody*)m->dBodies, (const DevDof*)m->dDofs, (const DevKinEntry*)k->dEntries, (const int32_t*)k->dPath, k->count,
-                     m->nb, m->n, k->P, B, q, grad_q, grad_damping, grad_target, accumulate ? 1 : 0, free_count, (double*)workspace);
-  HIP_TRY(hipGetLastError());
-  return NBL_OK;
-}
+}  // extern "C"

@@ -77,24 +77,3 @@ static void endTiming(nbl_tree_model* m, hipStream_t s) {
 static const bool g_dbgSync = getenv("NBL_DEBUG_SYNC") && atoi(getenv("NBL_DEBUG_SYNC")) != 0;
 #define TIMED(kid, launch) do { beginTiming(m, s, kid); launch; endTiming(m, s); \
     if (g_dbgSync) { const hipError_t de_ = hipStreamSynchronize(s); fprintf(stderr, "[nbl] %s: %s\n", kKernelNames[kid], hipGetErrorString(de_)); } } while (0)
-
-// The task-space calls (csrc/taskspace.hip): nimble_amd_tree.hip defines them once, on the base of a handle; the entry points nbl_task_* of
-// include/nimble_amd.h are thin forwards to them in every instantiation (nimble_amd.hip) and reach callers through the dispatcher.
-struct nbl_kin_map;
-size_t treeTaskWorkspaceBytes(const nbl_tree_model* m, int64_t B);
-int32_t treeTaskJacobian(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* J, void* stream);
-int32_t treeTaskJacobianDeriv(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, double* Jdot,
-                              void* stream);
-int32_t treeTaskJacobianVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* G,
-                            double* grad_q, int32_t accumulate, void* stream);
-int32_t treeTaskAccel(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
-                      double* bias, double* xdd, void* stream);
-int32_t treeTaskAccelVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, int32_t rows, int32_t n, const double* state, const double* accel,
-                         const double* g_out, double* grad_state, double* grad_accel, int32_t accumulate, void* workspace,
-                         size_t workspace_bytes, void* stream);
-
-// The reverse pass of inverse kinematics (csrc/ik_grad.hip) goes the same way: defined once in nimble_amd_tree.hip, forwarded to by
-// nbl_ik_grad_workspace_bytes / nbl_ik_solve_vjp of every instantiation.
-size_t treeIkGradWorkspaceBytes(const nbl_tree_model* m, const nbl_kin_map* k, int64_t B);
-int32_t treeIkSolveVjp(nbl_tree_model* m, const nbl_kin_map* k, int64_t B, const double* q, const double* grad_q, double grad_damping,
-                       double* grad_target, int32_t accumulate, int32_t* free_count, void* workspace, size_t workspace_bytes, void* stream);

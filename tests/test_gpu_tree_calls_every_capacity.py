@@ -1,5 +1,5 @@
-"""The contact-independent calls (csrc/nimble_amd_tree.hip: kinematics, dynamics, wrenches, IK, centroidal quantities, sensors) are built
-once and work on the capacity-independent base of a handle that one of FOUR instantiations of the contact stage owns (csrc/abi_variants.h,
+"""The contact-independent calls (csrc/nimble_amd_tree.hip: kinematics, dynamics, wrenches, IK and its reverse pass, centroidal quantities,
+sensors, task-space Jacobians and accelerations) are built once and work on the capacity-independent base of a handle that one of FOUR instantiations of the contact stage owns (csrc/abi_variants.h,
 csrc/tree_model_host.hpp).  Every other dynamics / kinematics test creates collider-free models, which always land in the 8-slot build; here
 the same model is created in all four (NBL_MIN_VARIANT = 0..3, read at every nbl_model_create) and every call is run on all four handles.
 
@@ -15,6 +15,9 @@ AGAINST THE REFERENCE, on the handle of the 8-slot build, at the tolerance and w
   map_to_pos / map_to_vel / the position VJP                 kin_numpy, 1e-12 / 1e-10   test_gpu_kinematics
   centroidal outputs, sensor readings                        cen_numpy / sens_numpy, 1e-10   test_gpu_centroidal, test_gpu_sensors
   solve_ik, max_step_count = 20                              the host build, 1e-9, equal step counts (up to 25 steps: test_ik_host) test_gpu_ik
+  task_jacobian, task_jacobian_deriv, map_to_acc             task_numpy, FORWARD_TOL; reverse passes: 100 x the scatter of the reference's
+                                                             own central differences                     test_gpu_taskspace
+  solve_ik_vjp at the solver's poses                         ik_grad_numpy, 10 d, cond(J_F) <= 1e3 in every world   test_gpu_ik_grad
 The other VJPs are held bitwise to the 8-slot handle's, which is the build every existing VJP test already runs against its reference."""
 import copy
 import ctypes as C
@@ -60,13 +63,15 @@ def rig():
     ow = OracleWorld(md)
     S, A, g = _states(md, 4 * B, 11)
     # the spatial entry's rotation at least 0.3 rad below pi, as test_gpu_kinematics keeps it (logMap loses digits there)
-    keep = [b for b in range(4 * B)
-            if np.arccos(np.clip(0.5 * (np.trace(ow.body_world_transform(S[b, :n], ball)[:3, :3]) - 1), -1, 1)) < np.pi - 0.3][:B]
+    pool = [b for b in range(4 * B)
+            if np.arccos(np.clip(0.5 * (np.trace(ow.body_world_transform(S[b, :n], ball)[:3, :3]) - 1), -1, 1)) < np.pi - 0.3]
+    keep = pool[:B]
     assert len(keep) == B
     rng = np.random.default_rng(12)
     mp = pytest.MonkeyPatch()
     mp.setenv("NBL_MIN_VARIANT", "0")
     r = {"md": md, "n": n, "ball": ball, "entries": entries, "ow": ow, "S": S[keep], "A": A[keep], "g": g[keep], "worlds": _worlds(md),
+         "pool": S[pool],                                          # every pose with the log-map margin: the reverse pass of IK picks from it
          "W": rng.normal(0, 3.0, (B, 6)), "F": rng.normal(0, 1.0, (B, 3)), "G": rng.normal(0, 1.0, (B, n, n)), "gp": rng.normal(0, 1.0, (B, 9))}
     yield r
     mp.undo()
@@ -209,6 +214,70 @@ def test_solve_ik(rig):
     assert np.array_equal(steps, hs) and float(np.abs(q - hq).max()) <= 1e-9
 
 
+def test_task_space_jacobians_and_accelerations(rig):
+    import nimblephysics_amd as na
+    import task_cases as tc
+    import task_numpy as tn
+    from test_gpu_taskspace import FORWARD_TOL
+    S, A, n, md, entries = rig["S"], rig["A"], rig["n"], rig["md"], rig["entries"]
+    R = tc.rows(entries)
+    rng = np.random.default_rng(31)
+    cot, G = rng.normal(size=(B, R)), rng.normal(size=(B, R, n))
+    maps = {id(w): _mapping(w, entries) for w in rig["worlds"]}
+
+    def call(w):
+        s1, a1, s2 = _t(S, True), _t(A, True), _t(S, True)
+        xdd = na.map_to_acc(w, maps[id(w)], s1, a1); xdd.backward(_t(cot))
+        J = na.task_jacobian(w, maps[id(w)], s2); J.backward(_t(G))
+        return J, na.task_jacobian_deriv(w, maps[id(w)], _t(S)), xdd, s1.grad, a1.grad, s2.grad
+    J, Jd, xdd, gs, ga, gj = _on_every_handle(rig["worlds"], call)
+    assert J.shape == (B, R, n) and not gj[:, n:].any()
+    m, ne, q, v = tn.Model(md), tc.numpy_entries(entries), S[:, :n], S[:, n:]
+    Jr, Jdr = tn.jacobians(m, ne, q, v)
+    for what, got, ref in (("J", J, Jr), ("Jdot", Jd, Jdr), ("xdd", xdd, tn.accel(m, ne, q, v, A))):
+        e = tc.err(got, ref)
+        print(what, "largest per-world deviation:", float(e.max()))
+        assert (e <= FORWARD_TOL).all(), (what, int(e.argmax()), float(e.max()))
+    fd = {eps: tn.fd_accel_vjp(m, ne, q, v, A, cot, eps) + (tn.fd_jacobian_vjp(m, ne, q, G, eps),) for eps in (1e-5, 1e-6)}
+    for k, (what, got) in enumerate((("xdd q", gs[:, :n]), ("xdd v", gs[:, n:]), ("xdd a", ga), ("J q", gj[:, :n]))):
+        scatter = float(tc.err(fd[1e-5][k], fd[1e-6][k]).max())
+        e = tc.err(got, fd[1e-6][k])
+        print(what, "device against the 1e-6 differences:", float(e.max()), "reference differences, 1e-5 against 1e-6:", scatter)
+        assert (e <= 100.0 * scatter).all(), (what, int(e.argmax()), float(e.max()), 100.0 * scatter)
+
+
+def test_solve_ik_and_its_reverse_pass(rig):
+    """the first 65 poses of the rig's pool whose solve (20 steps from zero, the host build's) ends at a pose with cond(J_F) <= 1e3: the
+    condition of ik_grad_cases' tolerance rule, met by the choice of inputs; gc.reference asserts it again at the device's own poses"""
+    import ik_cases as ic
+    import ik_grad_cases as gc
+    import ik_grad_numpy as ign
+    import nimblephysics_amd as na
+    from kin_numpy import mapping_rows
+    n, ow, md, entries, pool = rig["n"], rig["ow"], rig["md"], rig["entries"], rig["pool"]
+    h = gc.HostIKGrad(ic.load_ik_shim(), gc.load_grad_shim(), md, entries)
+    targets = np.stack([mapping_rows(ow, md, s[:n], entries)[0] for s in pool])
+    hq = h.solve(targets, max_step_count=20)[0]
+    gq = np.random.default_rng(32).normal(0, 1, hq.shape)
+    lo, hi = gc.limits(md)
+    cond = ign.vjp_batch(h.evaluate(hq, targets)[1], gq, hq, lo, hi, 1e-9)[3]
+    pick = np.flatnonzero(cond <= gc.COND_MAX)[:B]
+    assert len(pick) == B, (len(pool), int((cond <= gc.COND_MAX).sum()))
+    targets, gq = targets[pick], gq[pick]
+    maps = {id(w): _mapping(w, entries) for w in rig["worlds"]}
+
+    def call(w):
+        q, loss, steps = na.solve_ik(w, maps[id(w)], _t(targets), None, na.IKConfig(max_step_count=20))
+        gt, free = na.solve_ik_vjp(w, maps[id(w)], q, _t(gq))
+        return q, steps, gt, free
+    q, steps, gt, free = _on_every_handle(rig["worlds"], call)
+    assert float(np.abs(q - hq[pick]).max()) <= 1e-9
+    want, d, cnt, worst = gc.reference(h, md, q, gq, 1e-9)
+    err = float(np.abs(gt - want).max())
+    print(f"solve_ik_vjp: |F| in [{cnt.min()}, {cnt.max()}], worst cond(J_F) {worst:.1f}, NumPy forms disagree by {d:.3e}, device off by {err:.3e}")
+    assert np.array_equal(free, cnt) and np.isfinite(gt).all() and err <= 10.0 * d
+
+
 def test_inertia_patches_reach_the_base_of_every_handle(rig):
     """nbl_set_body_inertia writes into the instantiation's handle; the mass matrix call reads the base of the same handle."""
     import nimblephysics_amd as na
@@ -259,6 +328,16 @@ def test_a_map_or_set_of_another_instantiation_is_refused(rig):
     assert L.nbl_centroidal_forward(w1._h, bs0, B, p(s), N, 0, p(o3), N, N, N, N, N, N, p(ws), ws.numel(), None) == -1
     assert b"the body set was made for another model" in L.nbl_last_error()
     assert L.nbl_centroidal_forward(w0._h, bs0, B, p(s), N, 0, p(o3), N, N, N, N, N, N, p(ws), ws.numel(), None) == 0
+    J = torch.empty((9 * n, B), dtype=torch.float64, device=DEV)
+    assert L.nbl_task_jacobian(w1._h, km0, B, 9, n, p(s), p(J), None) == -1
+    assert L.nbl_last_error() == b"the kinematics map was made for another model"
+    assert L.nbl_task_jacobian(w0._h, km0, B, 9, n, p(s), p(J), None) == 0
+    need = L.nbl_ik_grad_workspace_bytes(w0._h, km0, B)
+    iws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    qz, gt = torch.zeros((n, B), dtype=torch.float64, device=DEV), torch.empty((9, B), dtype=torch.float64, device=DEV)
+    assert L.nbl_ik_solve_vjp(w1._h, km0, B, p(qz), p(qz), 1e-9, p(gt), 0, None, p(iws), need, None) == -1
+    assert L.nbl_last_error() == b"the kinematics map was made for another model"
+    assert L.nbl_ik_solve_vjp(w0._h, km0, B, p(qz), p(qz), 1e-9, p(gt), 0, None, p(iws), need, None) == 0
     torch.cuda.synchronize()
 
 

@@ -1,7 +1,8 @@
 """Every function include/nimble_amd.h declares - nbl_ik_default_config included - exists in EVERY build of the library, and in exactly one
 place.  The calls that depend on the contact capacity are defined in nimble_amd.hip and renamed per instantiation (csrc/abi_variants.h); the
-contact-independent ones (kinematics, dynamics, IK, centroidal, sensors) are defined once, in nimble_amd_tree.hip, under their public names:
-never renamed, never in the dispatcher's table.  nimble_amd.hip alone, which then includes nimble_amd_tree.hip, is the whole library in its
+43 contact-independent ones (kinematics, dynamics, IK and its reverse pass, centroidal, sensors, task space) are defined once, in
+nimble_amd_tree.hip, under their public names: never renamed, never in the dispatcher's list of per-capacity entry points (NBL_PER_CAPACITY,
+from which the prototypes, the table's members and its rows are expanded).  nimble_amd.hip alone, which then includes nimble_amd_tree.hip, is the whole library in its
 8-contact form (the developer builds of tools/ compile it that way and load it through NBL_LIB_PATH)."""
 import os
 import re
@@ -34,9 +35,11 @@ def test_every_public_symbol_is_defined_in_the_single_unit_library():
         else:
             n_once += 1
             assert sym not in renamed, f"{sym} is built once (nimble_amd_tree.hip) but renamed in abi_variants.h"
-            assert sym + "##S" not in disp and "(*%s)" % sym[4:] not in disp and not _defines(sym, disp), \
+            assert not re.search(r"\bX\(\s*S\s*,[^,]*,\s*%s\s*," % sym[4:], disp) and sym + "_c" not in disp and not _defines(sym, disp), \
                 f"{sym} is built once but still passes through the dispatcher"
-    assert n_once == 35
+    assert n_once == 43
+    for f in os.listdir(CSRC):                 # the forwards the task-space calls and the reverse pass of IK once went through
+        assert not re.search(r"\btree(Task|Ik)", open(os.path.join(CSRC, f)).read()), f
     # the stand-alone library (nimble_amd.hip without NBL_VARIANT_SUFFIX) takes the rest from the same file
     assert re.search(r'^#else\n(//[^\n]*\n)*#define NBL_TREE_STANDALONE\n#include "nimble_amd_tree.hip"\n#endif', per_capacity, re.M)
     for sym in ("nbl_ik_default_config", "nbl_ik_workspace_bytes", "nbl_ik_solve"):
